@@ -23,9 +23,17 @@ HBM, no collective on the data path:
       contiguous shards, one per GPU; `value` = 10 000 x K / max-over-ranks time.
   --scaling weak: every GPU searches its own 10 000-query batches.
 
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the configuration). --full adds everything else the line has
+carried: the device-resident kernel leg and its roofline, the counted passes, end-to-end and batch-1 latency,
+recall vs exact, the fixed-recall operating points, cpu_baseline and, for N>1, the one-batch-at-a-time,
+replica and sharded-identity legs; the --no-* options below skip legs of a --full run.
+--dump-outputs DIR writes the rows the timed path returned in its last step (scores.npy f32, ids.npy and
+counts.npy f64, rows.npy = their query rows; `_rank<r>` suffixes for N>1).
+
 Real data instead of synthetic: --documents documents.bin --queries-file queries.bin
-[--groundtruth groundtruth.tsv] [--results-tsv out.tsv] (Seismic's inner format and the TSV of
-perf_inverted_index).
+[--full --groundtruth groundtruth.tsv] [--full --results-tsv out.tsv] (Seismic's inner format and the TSV
+of perf_inverted_index).
 
 Prints ONE JSON line on rank 0 (fields: DESIGN.md "Measurement").
 """
@@ -117,7 +125,15 @@ def parse_args():
     ap.add_argument("--queries-file", default="", help="queries.bin (inner format) instead of synthetic queries")
     ap.add_argument("--groundtruth", default="", help="groundtruth.tsv: accuracy as scripts/run_experiments.py computes it")
     ap.add_argument("--results-tsv", default="", help="write query_idx\\tdoc_id\\trank\\tscore of the first batch here")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the timed steps (kernel leg, roofline, latency, recall, operating "
+                         "points, cpu_baseline, N>1 legs); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the rows the timed path returned in its last step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if (args.groundtruth or args.results_tsv) and not args.full:
+        ap.error("--groundtruth and --results-tsv belong to a --full run")
+    return args
 
 
 def workload_key(args, world, scaling):
@@ -226,6 +242,23 @@ def run_calls(calls, n_threads):
     if errs:
         raise errs[0]
     return dt
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # (the four .npy files, headers included, stay under 64 MB)
+
+
+def dump_outputs(dirname, scores, ids, counts, suffix=""):
+    """--dump-outputs: one step's result rows as a caller receives them (scores f32 [nq, k], ids and counts as f64, exact
+    below 2^53) plus rows.npy, the query rows written: all of them, or a fixed sample (seed 0) that fits DUMP_LIMIT_BYTES."""
+    nq = len(counts)
+    row_bytes = scores.shape[1] * (4 + 8) + 8 + 8
+    rows = np.arange(nq)
+    if nq * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("scores", scores[rows].astype(np.float32)), ("ids", ids[rows].astype(np.float64)),
+                    ("counts", counts[rows].astype(np.float64)), ("rows", rows.astype(np.float64))):
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
 
 
 def main():
@@ -400,6 +433,8 @@ def main():
 
     # ---------------- timed region: K calls of the entry point (host buffers in and out) ----------------
     timed_ids = sorted({(args.warmup + i) % n_batches for i in range(args.steps)})
+    last = (args.warmup + args.steps - 1) % n_batches   # the batch of the last timed step
+    dump_suffix = "" if world == 1 else "_rank%d" % rank
     elapsed, entry_results = None, {}
     if not args.no_entry:
         run_calls([entry_call(i) for i in range(args.warmup)], n_threads)
@@ -413,11 +448,13 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         entry_results = {bi: tuple(a.copy() for a in outs[bi]) for bi in timed_ids[:1]}
+        if args.dump_outputs:   # (before any later leg writes into the same rows)
+            dump_outputs(args.dump_outputs, outs[last][0], outs[last][1], outs[last][2][:my_q], dump_suffix)
     # N > 1, BASELINE configs[3] read literally: ONE batch at a time - a barrier before and after every step, each rank
     # issues its shard as one call from one thread, so no call of a later batch hides a rank's host side or fills its
     # launch tail. Reported NEXT to `value` (whose K calls are issued back to back from the request threads).
     one_at_a_time = None
-    if world > 1 and scaling == "strong" and not args.no_entry:
+    if args.full and world > 1 and scaling == "strong" and not args.no_entry:
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -429,71 +466,33 @@ def main():
         one_at_a_time = float(t.item())
 
     # ---------------- kernel leg (roofline): the same batches resident in HBM, HIP events around each launch ----------------
-    def step(i):
-        batches[i % n_batches].run(args.k, args.query_cut, args.heap_factor, srt, sync=False)
+    if args.full or args.no_entry:
+        def step(i):
+            batches[i % n_batches].run(args.k, args.query_cut, args.heap_factor, srt, sync=False)
 
-    for i in range(args.warmup):
-        step(i)
-    batches[0].sync()
-    barrier()
-    tk0 = time.perf_counter()
-    for i in range(args.steps):
-        step(args.warmup + i)
-    sync_stats = batches[0].sync()   # waits for the K launches; mean kernel duration from HIP events
-    barrier()
-    k_elapsed = time.perf_counter() - tk0
-    if world > 1:
-        t = torch.tensor([k_elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        k_elapsed = float(t.item())
-    kernel_ms = float(sync_stats.kernel_ms)
-    if elapsed is None:   # --no-entry: the kernel leg is the timed region
-        elapsed = k_elapsed
+        for i in range(args.warmup):
+            step(i)
+        batches[0].sync()
+        barrier()
+        tk0 = time.perf_counter()
+        for i in range(args.steps):
+            step(args.warmup + i)
+        sync_stats = batches[0].sync()   # waits for the K launches; mean kernel duration from HIP events
+        barrier()
+        k_elapsed = time.perf_counter() - tk0
+        if world > 1:
+            t = torch.tensor([k_elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            k_elapsed = float(t.item())
+        kernel_ms = float(sync_stats.kernel_ms)
+        if elapsed is None:   # --no-entry: the kernel leg is the timed region
+            elapsed = k_elapsed
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, *batches[last].fetch(args.k), dump_suffix)
 
-    # ---------------- accounting (outside the timed region) ----------------
-    # every timed batch gets one extra pass with the visited set materialised (sgpu_batch_run_counted):
-    # identical results, and work counters that exclude re-encountered documents exactly as the
-    # reference does -> algorithmic bytes of each launch
-    # bytes per document element as stored: f16 2 + 2, fixed-u8 2 + 1, DotVByte 1.5 (12-byte slices of eight components) + 1
-    val_bytes = 2 if args.value_type == "f16" else 1
-    doc_comp_bytes = None
-    if args.value_type == "dotvbyte":   # 1.5 bytes per component in a packed slice, 2 for the documents that keep the raw form
-        raw_docs, raw_elems = index.stream_stats()
-        raw_share = raw_elems / float(max(int(d.nnz), 1))
-        doc_comp_bytes = 1.5 * (1.0 - raw_share) + 2.0 * raw_share
-    algo, counted_identical, results = [], True, {}
-    entry_identical = True
-    agg = np.zeros(8, np.float64)
-    for bi in timed_ids:
-        b = batches[bi]
-        gsc, gid, gn = b.fetch(args.k)
-        if bi in entry_results:   # the entry point's rows are the device-resident launch's rows
-            esc, eid, en = entry_results[bi]
-            entry_identical &= bool(np.array_equal(en[:my_q], gn) and np.array_equal(eid, gid)
-                                    and np.array_equal(esc.view(np.uint32), gsc.view(np.uint32)))
-        if args.no_accounting:
-            results[bi] = (gsc, gid, gn)
-            algo.append(0)
-            continue
-        b.run_counted(args.k, args.query_cut, args.heap_factor, srt)
-        csc, cid, cn = b.fetch(args.k)
-        counted_identical &= bool(np.array_equal(cn, gn) and np.array_equal(cid, gid)
-                                  and np.array_equal(csc.view(np.uint32), gsc.view(np.uint32)))
-        ab, counters = b.algorithmic_bytes(args.k, args.comp_width, val_bytes, doc_comp_bytes)
-        algo.append(ab)
-        agg += counters[:, :8].sum(axis=0)
-        results[bi] = (gsc, gid, gn)
-    nq_counted = max(1, my_q * len(timed_ids))
-    algo_bytes = float(np.mean(algo))
     ms_per_step = elapsed * 1e3 / args.steps
     qps = total_q_per_step * args.steps / elapsed
-    achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
     key = workload_key(args, world, scaling)
-    traffic_bytes, traffic_note = args.traffic_bytes, None
-    if traffic_bytes is None and world == 1:
-        traffic_bytes, traffic_note = recorded_traffic(key)
-    first = timed_ids[0]
-    gsc, gid, gn = results[first]
     out = {
         "metric": METRIC,
         "value": qps,
@@ -531,38 +530,95 @@ def main():
             "parallelism": "index replicated, %s, no collective" % (
                 ("each batch of %d cut into %d contiguous shards" % (args.queries, world)) if scaling == "strong" and world > 1
                 else ("%d batch(es) of %d per step" % (world, args.queries))),
-            "launch": {"grid": int(sync_stats.grid), "block": int(sync_stats.block),
-                       "lds_bytes": int(sync_stats.lds_bytes), "queries_per_launch": my_q},
             "timed_region": ("K calls of sgpu_batch_search (host buffers in and out) from %d request thread(s)" % n_threads)
             if not args.no_entry else "--no-entry: K device-resident launches (profiling run)",
         },
-        "entry_point": {"name": "sgpu_batch_search", "host_threads": n_threads, "queries_per_call": my_q,
-                        "rows_identical_to_device_resident_launch": entry_identical},
-        "device_resident": {"value": total_q_per_step * args.steps / k_elapsed, "unit": "queries/s",
-                            "ms_per_step": k_elapsed * 1e3 / args.steps,
-                            "note": "the same batches already in HBM, results left in HBM: one kernel launch per step (the r01/r02 `value`)"},
+        "entry_point": {"name": "sgpu_batch_search", "host_threads": n_threads, "queries_per_call": my_q},
         "library": _native.build_info() + (" (matches this tree)" if _native.source_fingerprint() in _native.build_info() else " (NOT the build of this tree: %s)" % _native.source_fingerprint()),
-        "roofline": {
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBPS,
-            "traffic": traffic_bytes,
-            "traffic_note": traffic_note,
-            "kernel": "seismic_search_kernel",
-            "kernel_source_id": kernel_source_id(),
-            "measured_on": "device-resident launches of the timed batches (HIP events on the library's stream)",
-            "kernel_ms": kernel_ms,
-            "algorithmic_bytes_per_launch": algo_bytes,
-            "bytes_per_query": algo_bytes / max(my_q, 1),
-            "docs_scored_per_query": agg[5] / nq_counted,
-            "docs_scored_speculatively_per_query": agg[7] / nq_counted,
-            "summary_entries_per_query": agg[2] / nq_counted,
-            "counted_pass_identical": counted_identical,
-            "launches_accounted": len(timed_ids),
-        },
         "timing_s": {"generate": t_gen, "build": t_build, "upload": t_up},
+    }
+    if world > 1:
+        out["value_is"] = ("pipelined: the K sharded batches are issued back to back from %d request thread(s) per rank, so "
+                           "calls of consecutive batches overlap on a GPU" % n_threads)
+        out["host_threads_per_rank_for_host_phases"] = os.environ.get("SGPU_HOST_THREADS")
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # ---------------- accounting (outside the timed region) ----------------
+    # every timed batch gets one extra pass with the visited set materialised (sgpu_batch_run_counted):
+    # identical results, and work counters that exclude re-encountered documents exactly as the
+    # reference does -> algorithmic bytes of each launch
+    # bytes per document element as stored: f16 2 + 2, fixed-u8 2 + 1, DotVByte 1.5 (12-byte slices of eight components) + 1
+    val_bytes = 2 if args.value_type == "f16" else 1
+    doc_comp_bytes = None
+    if args.value_type == "dotvbyte":   # 1.5 bytes per component in a packed slice, 2 for the documents that keep the raw form
+        raw_docs, raw_elems = index.stream_stats()
+        raw_share = raw_elems / float(max(int(d.nnz), 1))
+        doc_comp_bytes = 1.5 * (1.0 - raw_share) + 2.0 * raw_share
+    algo, counted_identical, results = [], True, {}
+    entry_identical = True
+    agg = np.zeros(8, np.float64)
+    for bi in timed_ids:
+        b = batches[bi]
+        gsc, gid, gn = b.fetch(args.k)
+        if bi in entry_results:   # the entry point's rows are the device-resident launch's rows
+            esc, eid, en = entry_results[bi]
+            entry_identical &= bool(np.array_equal(en[:my_q], gn) and np.array_equal(eid, gid)
+                                    and np.array_equal(esc.view(np.uint32), gsc.view(np.uint32)))
+        if args.no_accounting:
+            results[bi] = (gsc, gid, gn)
+            algo.append(0)
+            continue
+        b.run_counted(args.k, args.query_cut, args.heap_factor, srt)
+        csc, cid, cn = b.fetch(args.k)
+        counted_identical &= bool(np.array_equal(cn, gn) and np.array_equal(cid, gid)
+                                  and np.array_equal(csc.view(np.uint32), gsc.view(np.uint32)))
+        ab, counters = b.algorithmic_bytes(args.k, args.comp_width, val_bytes, doc_comp_bytes)
+        algo.append(ab)
+        agg += counters[:, :8].sum(axis=0)
+        results[bi] = (gsc, gid, gn)
+    nq_counted = max(1, my_q * len(timed_ids))
+    algo_bytes = float(np.mean(algo))
+    achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+    traffic_bytes, traffic_note = args.traffic_bytes, None
+    if traffic_bytes is None and world == 1:
+        traffic_bytes, traffic_note = recorded_traffic(key)
+    first = timed_ids[0]
+    gsc, gid, gn = results[first]
+    out["config"]["launch"] = {"grid": int(sync_stats.grid), "block": int(sync_stats.block),
+                               "lds_bytes": int(sync_stats.lds_bytes), "queries_per_launch": my_q}
+    out["entry_point"]["rows_identical_to_device_resident_launch"] = entry_identical
+    out["device_resident"] = {"value": total_q_per_step * args.steps / k_elapsed, "unit": "queries/s",
+                              "ms_per_step": k_elapsed * 1e3 / args.steps,
+                              "note": "the same batches already in HBM, results left in HBM: one kernel launch per step (the r01/r02 `value`)"}
+    out["roofline"] = {
+        "bound": "hbm",
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBPS,
+        "traffic": traffic_bytes,
+        "traffic_note": traffic_note,
+        "kernel": "seismic_search_kernel",
+        "kernel_source_id": kernel_source_id(),
+        "measured_on": "device-resident launches of the timed batches (HIP events on the library's stream)",
+        "kernel_ms": kernel_ms,
+        "algorithmic_bytes_per_launch": algo_bytes,
+        "bytes_per_query": algo_bytes / max(my_q, 1),
+        "docs_scored_per_query": agg[5] / nq_counted,
+        "docs_scored_speculatively_per_query": agg[7] / nq_counted,
+        "summary_entries_per_query": agg[2] / nq_counted,
+        "counted_pass_identical": counted_identical,
+        "launches_accounted": len(timed_ids),
     }
     if world > 1:
         # every rank's kernel leg (its shard resident in HBM, HIP events): the first 8-GPU run shows at once whether a GPU lags
@@ -570,9 +626,6 @@ def main():
         t[rank] = kernel_ms
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         out["kernel_ms_per_rank"] = [round(float(x), 4) for x in t.tolist()]
-        out["value_is"] = ("pipelined: the K sharded batches are issued back to back from %d request thread(s) per rank, so "
-                           "calls of consecutive batches overlap on a GPU" % n_threads)
-        out["host_threads_per_rank_for_host_phases"] = os.environ.get("SGPU_HOST_THREADS")
     if one_at_a_time is not None:
         out["value_one_batch_at_a_time"] = args.queries * args.steps / one_at_a_time
         out["one_batch_at_a_time"] = {
@@ -979,11 +1032,7 @@ def main():
             "implementation": "oracle/seismic_oracle.cpp search_one<true>: AVX2+F16C scorer, hash-set visited set, range prefetch",
         }
         out["gpu_over_cpu_allcore"] = qps / qpsn if qpsn > 0 else None
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

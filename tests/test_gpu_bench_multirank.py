@@ -28,7 +28,7 @@ def _run(scaling, tmp_path, **extra_env):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
            "3", "--warmup", "1", "--docs", "60000", "--queries", "1501", "--n-postings", "300", "--scaling", scaling,
-           "--no-cpu", "--no-recall", "--no-latency", "--no-e2e"]
+           "--full", "--no-cpu", "--no-recall", "--no-latency", "--no-e2e"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -87,7 +87,7 @@ def test_bench_on_files_in_the_reference_formats(tmp_path):
     _native.write_results_tsv(gp, es, ei, en)
     env = dict(os.environ, SGPU_INDEX_CACHE=str(tmp_path))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--documents", dp, "--queries-file", qp, "--groundtruth", gp,
-           "--results-tsv", rp, "--n-postings", "300", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-latency", "--no-e2e",
+           "--results-tsv", rp, "--n-postings", "300", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-latency", "--no-e2e",
            "--target-recall", "0.5,0.999999"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -106,3 +106,37 @@ def test_bench_on_files_in_the_reference_formats(tmp_path):
     ix.upload(0)                                            # the TSV holds exactly what the API returns
     gs, gi, gn = ix.batch_search(*q, 10, 4, 1.0, False)
     assert [int(x) for x in gi[7, :gn[7]]] == res[7]
+
+
+def test_plain_run_reports_the_timed_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the line is the headline alone, and --dump-outputs holds the rows the last timed step returned:
+    those of sgpu_batch_search on the same batch of the seeded query stream, against the index the run saved."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from seismic_amd import _native
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--docs", "60000", "--queries", "700",
+           "--n-postings", "300", "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, env=dict(os.environ, SGPU_INDEX_CACHE=str(tmp_path)), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["unit"] == "queries/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["ms_per_step"] > 0 and out["value"] == pytest.approx(700 * 1e3 / out["ms_per_step"])
+    assert not {"roofline", "device_resident", "end_to_end", "latency", "recall_at_k", "operating_points", "cpu_baseline"} & set(out)
+    got = {n: np.load(str(dump / (n + ".npy"))) for n in ("scores", "ids", "counts", "rows")}
+    assert got["scores"].dtype == np.float32 and got["ids"].dtype == np.float64 and got["counts"].dtype == np.float64
+    assert np.array_equal(got["rows"], np.arange(700))
+    idx = [f for f in os.listdir(tmp_path) if f.endswith(".idx")]
+    assert len(idx) == 1, idx
+    ix = _native.NativeIndex.load(str(tmp_path / idx[0]))
+    ix.upload(0)
+    docs = _native.synth(60000, int(ix.desc.dim), 42, 0)
+    q_off, q_comp, q_val = _native.synth(700 * 6, int(ix.desc.dim), 43, 1, docs)   # 6 distinct batches: one per step
+    lo, hi = 5 * 700, 6 * 700                                                      # the last step's (warm-up 2 + step 4)
+    o0, o1 = int(q_off[lo]), int(q_off[hi])
+    sc, ids, n = ix.batch_search((q_off[lo:hi + 1] - q_off[lo]).astype(np.uint64), q_comp[o0:o1], q_val[o0:o1], 10, 4, 1.0, False)
+    assert np.array_equal(got["counts"], n.astype(np.float64)) and n.max() > 0
+    assert np.array_equal(got["ids"], ids.astype(np.float64))
+    assert np.array_equal(got["scores"].view(np.uint32), sc.view(np.uint32))

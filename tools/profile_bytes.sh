@@ -7,7 +7,7 @@ REPO="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$REPO/$1/$2"; LABEL=$2; shift 2
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --no-entry --no-cpu --no-recall --no-latency --no-e2e --no-accounting --target-recall= --steps 6 --warmup 2 $*"
+BENCH="python $REPO/bench.py --full --no-entry --no-cpu --no-recall --no-latency --no-e2e --no-accounting --target-recall= --steps 6 --warmup 2 $*"
 # (PMC_SETS="A B;C" overrides the counter groups, one rocprofv3 pass each)
 IFS=';' read -ra SETS <<< "${PMC_SETS:-FETCH_SIZE;WRITE_SIZE;TCC_HIT_sum TCC_MISS_sum}"
 for C in "${SETS[@]}"; do

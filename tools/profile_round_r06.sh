@@ -27,10 +27,10 @@ python tools/latency_probe.py 8800000 > gpurun_out/r06_latency_probe.txt 2>&1
 python tools/shard_probe.py > gpurun_out/r06_shard_probe.txt 2>&1
 # the bench lines (the traffic entries above are not in pmc_traffic.json yet when these run: their lines are re-read by
 # tools/record_profile.py on the build host and say so)
-python bench.py > gpurun_out/r06_bench_final.json 2> gpurun_out/r06_bench_final.err
-python bench.py --collection clustered > gpurun_out/r06_bench_clustered.json 2> gpurun_out/r06_bench_clustered.err
-python bench.py --value-type fixedu8 --no-cpu --target-recall= > gpurun_out/r06_bench_fixedu8.json 2>/dev/null
-python bench.py --value-type dotvbyte --no-cpu --target-recall= > gpurun_out/r06_bench_dotvbyte.json 2>/dev/null
-python bench.py --first-sorted 1 --no-cpu --target-recall= > gpurun_out/r06_bench_first_sorted.json 2>/dev/null
-python bench.py $C5 --target-recall= > gpurun_out/r06_bench_c5_5M_200K.json 2>/dev/null
+python bench.py --full > ${T}_bench_final.json 2> ${T}_bench_final.err
+python bench.py --full --collection clustered > ${T}_bench_clustered.json 2> ${T}_bench_clustered.err
+python bench.py --full --value-type fixedu8 --no-cpu --target-recall= > ${T}_bench_fixedu8.json 2>/dev/null
+python bench.py --full --value-type dotvbyte --no-cpu --target-recall= > ${T}_bench_dotvbyte.json 2>/dev/null
+python bench.py --full --first-sorted 1 --no-cpu --target-recall= > ${T}_bench_first_sorted.json 2>/dev/null
+python bench.py --full $C5 --target-recall= > ${T}_bench_c5_5M_200K.json 2>/dev/null
 du -sh gpurun_out

@@ -9,7 +9,7 @@ OUT="$REPO/gpurun_out/$TAG"; mkdir -p "$OUT"
 export SGPU_INDEX_CACHE=/tmp SGPU_TEST_HOOKS=1
 for kv in "$@"; do export "$kv"; done
 cd "$REPO"
-LEAN="--no-entry --no-cpu --no-recall --no-latency --no-e2e --target-recall= --steps 20 --warmup 3"
+LEAN="--full --no-entry --no-cpu --no-recall --no-latency --no-e2e --target-recall= --steps 20 --warmup 3"
 python bench.py $LEAN > "$OUT/bench_survey.json" 2> "$OUT/bench_survey.err"
 python bench.py $LEAN --collection clustered > "$OUT/bench_clustered.json" 2> "$OUT/bench_clustered.err"
 if [ -f seismic_amd/libseismic_hip_prof.so ]; then

@@ -7,7 +7,7 @@ TAG="$1"; shift
 OUT="$REPO/gpurun_out/$TAG"; mkdir -p "$OUT"
 export SGPU_INDEX_CACHE=/tmp SGPU_TEST_HOOKS=1
 cd "$REPO"
-LEAN="--no-entry --no-cpu --no-recall --no-latency --no-e2e --target-recall= --steps 20 --warmup 3"
+LEAN="--full --no-entry --no-cpu --no-recall --no-latency --no-e2e --target-recall= --steps 20 --warmup 3"
 for L in "$@"; do
   if [ "$L" = "-" ]; then unset SGPU_LIB; N=product; else export SGPU_LIB="$REPO/seismic_amd/libseismic_hip_$L.so"; N=$L; fi
   for C in survey clustered; do
