@@ -13,8 +13,7 @@ extern "C" {
 /* team size a host-parallel phase takes for num_threads == 0 (hardware threads capped by the cgroup CPU quota) */
 uint32_t sgpu_debug_host_threads(void);
 /* how sgpu_batch_search cuts a call of nq queries into launches: bounds[2j], bounds[2j+1] = queries [q0, q1) of launch j */
-uint32_t sgpu_debug_chunk_plan(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t want_tail, uint32_t coop_max,
-                               uint32_t lanes_free, uint32_t* bounds);
+uint32_t sgpu_debug_chunk_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t lanes_free, uint32_t* bounds);
 /* the forward store as sgpu_index_upload packs it (document-major records) and every document's ref */
 sgpu_status sgpu_debug_pack_forward(const sgpu_index* idx, uint8_t* out_fwd, uint64_t cap, uint64_t* out_doc_ref,
                                     uint64_t* out_bytes);

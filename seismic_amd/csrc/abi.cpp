@@ -23,7 +23,6 @@ Lane* lane_acquire(DeviceIndex* d);
 Lane* lane_try_acquire(DeviceIndex* d);
 bool call_enter(DeviceIndex* d);
 void call_exit(DeviceIndex* d);
-uint32_t coop_auto_max_queries(const DeviceIndex* d);
 void lane_release(DeviceIndex* d, Lane* l);
 Lane* lane_main(DeviceIndex* d);
 sgpu_batch** lane_scratch(Lane* l);
@@ -217,7 +216,7 @@ sgpu_status sgpu_index_stream_stats(const sgpu_index* idx, uint64_t* raw_docs, u
   *raw_docs = *raw_elements = 0;
   try {
     std::vector<uint8_t> raw;
-    pack_dvb_raw_flags(idx->host, false, &raw);   // (empty unless the index is a DotVByte one)
+    pack_dvb_raw_flags(idx->host, &raw);   // (empty unless the index is a DotVByte one)
     for (uint64_t d = 0; d < raw.size(); ++d)
       if (raw[d]) {
         *raw_docs += 1;
@@ -306,34 +305,12 @@ sgpu_status sgpu_batch_fetch_stats(sgpu_index* idx, sgpu_batch* batch, uint32_t*
 
 void sgpu_batch_destroy(sgpu_batch* batch) { batch_free(batch); }
 
-// How a shard of nq queries is cut (pure: tests/test_abi_and_host.py checks it through sgpu_debug_chunk_plan).
-// chunk_jobs: the number of launches wanted before lanes are taken; *tail > 0 means "everything but the last *tail
-// queries, then those" (SGPU_TAIL_COOP, two launches). chunk_bounds: the queries [q0, q1) of launch j of n_jobs.
-static uint32_t chunk_jobs(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t want_tail, uint32_t coop_max,
-                           uint32_t* tail) {
-  uint32_t n_jobs = 1;
-  *tail = 0;
-  if (chunk_min && nq >= 2 * chunk_min) n_jobs = std::min<uint32_t>(chunk_max, nq / chunk_min);
-  if (n_jobs == 1 && want_tail && coop_max) {
-    const uint32_t t = std::min(want_tail, coop_max);
-    if (nq > coop_max + t && 2 * t < nq) {
-      *tail = t;
-      n_jobs = 2;
-    }
-  }
-  return n_jobs;
+// How a shard of nq queries is cut (pure: tests/test_abi_and_host.py checks it through sgpu_debug_chunk_bounds).
+// chunk_jobs: the number of launches wanted before lanes are taken. chunk_bounds: the queries [q0, q1) of launch j of n_jobs.
+static uint32_t chunk_jobs(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max) {
+  return chunk_min && nq >= 2 * chunk_min ? std::min<uint32_t>(chunk_max, nq / chunk_min) : 1u;
 }
-static void chunk_bounds(uint32_t nq, uint32_t n_jobs, uint32_t tail, uint32_t j, uint32_t* q0, uint32_t* q1, uint32_t first = 0) {
-  if (tail && n_jobs == 2) {
-    *q0 = j == 0 ? 0 : nq - tail;
-    *q1 = j == 0 ? nq - tail : nq;
-    return;
-  }
-  if (first && n_jobs == 2 && first < nq) {   // (two chunks, the first one of `first` queries)
-    *q0 = j == 0 ? 0 : first;
-    *q1 = j == 0 ? first : nq;
-    return;
-  }
+static void chunk_bounds(uint32_t nq, uint32_t n_jobs, uint32_t j, uint32_t* q0, uint32_t* q1) {
   *q0 = (uint32_t)((uint64_t)nq * j / n_jobs);
   *q1 = (uint32_t)((uint64_t)nq * (j + 1) / n_jobs);
 }
@@ -379,33 +356,14 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
   // with four / one, two threads 1.71 against 1.69 / 1.68; profiles/r06_entry_point_chunks.txt)
   const uint32_t chunk_max = chunk_max_env ? chunk_max_env : ((in_flight.shared || device_plan_applies(d, params)) ? 2u : 4u);
   Job jobs[8];
-  // Mid-size shards (SGPU_TAIL_COOP = n, an experiment, off by default): more queries than the cooperative variant takes
-  // on its own, fewer than two chunks - the last n queries go out as a second launch on another lane, small enough for
-  // the cooperative variant; its workgroups become resident as the first launch's run out of queries. Measured 7 %
-  // slower than one launch (profiles/r03_chunk_probe.txt).
-  uint32_t tail = 0;
-  uint32_t n_jobs;
-  {
-    const char* th = std::getenv("SGPU_TEST_HOOKS");   // (a test hook: honoured only while SGPU_TEST_HOOKS=1 is set)
-    const char* tv = (th && *th && *th != '0') ? std::getenv("SGPU_TAIL_COOP") : nullptr;
-    const uint32_t want = tv && *tv ? (uint32_t)std::strtoul(tv, nullptr, 10) : 0u;
-    // (r06: 1300 where the chunks are planned on the device - a 1250- or 2500-query call is then ONE launch: from two request
-    // threads 864 -> 781 us and 1551 -> 1475 us per call, from one thread no difference; profiles/r06_shard_probe_chunk_min.txt)
-    const uint32_t cmin = chunk_min != 0xffffffffu ? chunk_min : (device_plan_applies(d, params) ? 1300u : 600u);
-    n_jobs = chunk_jobs(nq, cmin, chunk_max, want, want ? coop_auto_max_queries(d) : 0u, &tail);
-  }
-  // (experiment, a test hook: SGPU_CHUNK_FIRST = share of the call, in per mille, that the first of two chunks takes)
-  uint32_t first = 0;
-  if (n_jobs == 2 && !tail) {
-    const char* th = std::getenv("SGPU_TEST_HOOKS");
-    const char* fv = (th && *th && *th != '0') ? std::getenv("SGPU_CHUNK_FIRST") : nullptr;
-    const uint32_t pm = fv && *fv ? (uint32_t)std::strtoul(fv, nullptr, 10) : 0u;
-    if (pm > 0 && pm < 1000) first = std::max<uint32_t>(1, (uint32_t)((uint64_t)nq * pm / 1000));
-  }
+  // (r06: 1300 where the chunks are planned on the device - a 1250- or 2500-query call is then ONE launch: from two request
+  // threads 864 -> 781 us and 1551 -> 1475 us per call, from one thread no difference; profiles/r06_shard_probe_chunk_min.txt)
+  const uint32_t cmin = chunk_min != 0xffffffffu ? chunk_min : (device_plan_applies(d, params) ? 1300u : 600u);
+  uint32_t n_jobs = chunk_jobs(nq, cmin, chunk_max);
   std::vector<uint64_t> off;   // a chunk's offsets, rebased (sized here: nothing below allocates host memory)
   if (n_jobs > 1) {
     try {
-      off.resize(first ? (size_t)nq + 2 : (size_t)nq / 2 + 2);
+      off.resize((size_t)nq / 2 + 2);
     } catch (const std::exception&) {
       n_jobs = 1;
     }
@@ -418,7 +376,6 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
       break;
     }
   }
-  if (n_jobs < 2) tail = 0;
   const uint32_t k = params.k;
   sgpu_status st = SGPU_OK;
   std::string msg;
@@ -430,7 +387,7 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
   }
   for (uint32_t j = 0; j < n_jobs && st == SGPU_OK; ++j) {
     Job& jb = jobs[j];
-    chunk_bounds(nq, n_jobs, tail, j, &jb.q0, &jb.q1, first);
+    chunk_bounds(nq, n_jobs, j, &jb.q0, &jb.q1);
     const uint64_t* qo = q_off;
     if (n_jobs > 1 && jb.q0 != 0) {   // (a chunk that starts at query 0 uses the caller's offsets as they are)
       for (uint32_t q = jb.q0; q <= jb.q1; ++q) off[q - jb.q0] = q_off[q] - q_off[jb.q0];
@@ -591,14 +548,11 @@ uint32_t sgpu_debug_host_threads(void) {
 
 // (not part of the boundary: how search_shard would cut a call of nq queries when `lanes_free` lanes can be had -
 // bounds[2 * j], bounds[2 * j + 1] = the queries [q0, q1) of launch j; returns the number of launches)
-uint32_t sgpu_debug_chunk_plan(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t want_tail, uint32_t coop_max,
-                               uint32_t lanes_free, uint32_t* bounds) {
+uint32_t sgpu_debug_chunk_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t lanes_free, uint32_t* bounds) {
   SGPU_HOOK_OR(0u);
-  uint32_t tail = 0;
-  uint32_t n_jobs = chunk_jobs(nq, chunk_min, chunk_max < 1 ? 1 : (chunk_max > 8 ? 8 : chunk_max), want_tail, coop_max, &tail);
+  uint32_t n_jobs = chunk_jobs(nq, chunk_min, chunk_max < 1 ? 1 : (chunk_max > 8 ? 8 : chunk_max));
   if (lanes_free >= 1 && n_jobs > lanes_free) n_jobs = lanes_free;
-  if (n_jobs < 2) tail = 0;
-  for (uint32_t j = 0; j < n_jobs; ++j) chunk_bounds(nq, n_jobs, tail, j, bounds + 2 * j, bounds + 2 * j + 1);
+  for (uint32_t j = 0; j < n_jobs; ++j) chunk_bounds(nq, n_jobs, j, bounds + 2 * j, bounds + 2 * j + 1);
   return n_jobs;
 }
 
@@ -611,10 +565,7 @@ sgpu_status sgpu_debug_pack_forward(const sgpu_index* idx, uint8_t* out_fwd, uin
   try {
     std::vector<uint8_t> raw, fwd;
     std::vector<uint64_t> off16, dref;
-    {   // (an f16 index: the layout sgpu_index_upload would choose - plain unless SGPU_FWD_STREAM=sliced)
-      const char* fs = std::getenv("SGPU_FWD_STREAM");
-      pack_dvb_raw_flags(idx->host, fs && std::string(fs) == "sliced", &raw);
-    }
+    pack_dvb_raw_flags(idx->host, &raw);
     pack_record_offsets(idx->host, raw, 128 / 16, &off16);
     *out_bytes = std::max<uint64_t>(off16[idx->host.n_docs] * 16, 16);
     if (!out_fwd) return SGPU_OK;

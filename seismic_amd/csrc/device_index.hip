@@ -29,21 +29,12 @@ hipError_t run_u32_packed_u8(const LaunchArgs& a, int* occupancy);
 hipError_t run_u32_split_u8(const LaunchArgs& a, int* occupancy);
 hipError_t run_u16_dense_dvb(const LaunchArgs& a, int* occupancy);
 hipError_t run_u16_packed_dvb(const LaunchArgs& a, int* occupancy);
-#ifdef SGPU_WITH_F16S   // (make WITH_F16S=1: the sliced layout of an f16 index - measured slower than the plain records, off by default)
-hipError_t run_u16_dense_f16s(const LaunchArgs& a, int* occupancy);
-hipError_t run_u16_packed_f16s(const LaunchArgs& a, int* occupancy);
-#endif
 
 static hipError_t run_any(const LaunchArgs& a, int* occ) {
   // (u16 components: dense byte table or packed {bits, rank} words. The hashed lookup is the u32 layout: for u16 it
   // measured slower than both - 6.46 against 5.81 ms per 10 000-query launch, profiles/r03_lds_sensitivity.md - and its
   // three families were dropped in r05)
   if (a.comp_width == 2 && a.lookup != LK_DENSE && a.lookup != LK_PACKED) return hipErrorInvalidConfiguration;
-#ifdef SGPU_WITH_F16S
-  if (a.value_type == kDevValF16Sliced) return a.lookup == LK_DENSE ? run_u16_dense_f16s(a, occ) : run_u16_packed_f16s(a, occ);
-#else
-  if (a.value_type == kDevValF16Sliced) return hipErrorInvalidConfiguration;
-#endif
   if (a.value_type == SGPU_VAL_DOTVBYTE)   // (u16 components only)
     return a.lookup == LK_DENSE ? run_u16_dense_dvb(a, occ) : run_u16_packed_dvb(a, occ);
   if (a.value_type == SGPU_VAL_FIXEDU8 && a.comp_width == 4) return a.lookup == LK_SPLIT ? run_u32_split_u8(a, occ) : run_u32_packed_u8(a, occ);
@@ -117,7 +108,6 @@ struct DeviceIndex {
   std::vector<uint32_t> list_nb, list_np;   // blocks / postings per posting list (host copy)
   uint32_t max_nb = 0;
   uint32_t value_type = SGPU_VAL_F16;   // how the records store document values
-  bool fwd_sliced = false;        // an f16 index in the sliced layout (compressed component stream: kernel VT_F16S)
   float val_scale = 0.0f;
   bool fwd_block_major = false;   // forward store holds a copy of every posting's record, block by block
   bool coop_broken = false;       // a cooperative launch reported a protocol error: the variant stays off for this replica
@@ -173,14 +163,6 @@ Lane* lane_acquire(DeviceIndex* d) {
       }
     d->pool_cv.wait(lk);
   }
-}
-
-// Largest launch the cooperative kernel variant is chosen for on its own (configure); 0 = switched off.
-uint32_t coop_auto_max_queries(const DeviceIndex* d) {
-  const char* cm = std::getenv("SGPU_COOP");
-  if (cm && !std::strcmp(cm, "0")) return 0;
-  const char* v = std::getenv("SGPU_COOP_MAX_NQ");
-  return v && *v ? (uint32_t)std::strtoul(v, nullptr, 10) : (uint32_t)d->n_cu;
 }
 
 // A free lane, or null: a call that already holds one lane never WAITS for another (two callers each
@@ -262,17 +244,16 @@ int device_count() {
 __global__ __launch_bounds__(256) void replicate_records_kernel(uint8_t* fwd, const uint64_t* __restrict__ doc_ref,
                                                                 const uint32_t* __restrict__ post_doc,
                                                                 const uint64_t* __restrict__ post_ref, uint64_t n_postings,
-                                                                uint32_t bytes_per_elem, uint32_t dvb, uint32_t val_bytes) {
+                                                                uint32_t bytes_per_elem, uint32_t dvb) {
   const uint64_t g = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const uint32_t sub = threadIdx.x & 15;
   const uint64_t n_groups = ((uint64_t)gridDim.x * blockDim.x) >> 4;
   for (uint64_t p = g; p < n_postings; p += n_groups) {
     const uint64_t dst = post_ref[p], src = doc_ref[post_doc[p]];
     uint32_t n16;   // 16-byte units of the record
-    if (dvb && !(dst & 0x8000u)) {   // sliced record (pack_index.cpp: record_bytes)
-      const uint32_t ns = (((uint32_t)dst & 0x7fffu) + 7u) >> 3, vb8 = 8u * val_bytes;
-      n16 = val_bytes == 1 ? (ns * 20u + 15u) >> 4                                          // DotVByte: [ns x 16 B][ns x 4 B]
-                           : ((((ns * 12u + vb8 - 1u) & ~(vb8 - 1u)) + ns * vb8) + 15u) >> 4;   // sliced f16
+    if (dvb && !(dst & 0x8000u)) {   // sliced DotVByte record: [ns x 16 B][ns x 4 B] (pack_index.cpp: record_bytes)
+      const uint32_t ns = (((uint32_t)dst & 0x7fffu) + 7u) >> 3;
+      n16 = (ns * 20u + 15u) >> 4;
     } else {
       const uint32_t len = (uint32_t)dst & (dvb ? 0x7fffu : 0xffffu);
       n16 = (((len + 7u) & ~7u) * bytes_per_elem + 15u) >> 4;
@@ -317,21 +298,8 @@ sgpu_status device_index_upload(const HostIndex& h, int device, DeviceIndex** ou
     // otherwise touch more lines than its size needs: at 16-byte alignment a 480-byte record straddles
     // ~4.75 lines, line-fitted 4.
     std::vector<uint64_t> rec_off16;
-    std::vector<uint8_t> dvb_raw;   // sliced layouts: the documents that keep the raw record form (a gap too wide for its field)
-    // SGPU_FWD_STREAM=sliced (libraries built with `make WITH_F16S=1` only): an f16 index over u16 components takes the
-    // SLICED layout - the DotVByte index's compressed component stream in front of the binary16 values, 28 bytes per
-    // 8-element slice instead of 32; lossless, rows bit-identical (kernel VT_F16S). Measured r05 on the 8.8M-document
-    // collection: 33.0 GB resident instead of 36.3 and 6.02 ms per 10 000-query launch instead of 5.94 - the decode costs
-    // more than the bytes return (profiles/r05_bytes_experiments.md); a footprint option, not in the default build.
-    {
-      const char* fs = std::getenv("SGPU_FWD_STREAM");
-      const bool want = fs && std::strcmp(fs, "sliced") == 0;
-#ifndef SGPU_WITH_F16S
-      if (want) return bail(fail(SGPU_EINVAL, "SGPU_FWD_STREAM=sliced needs a library built with `make WITH_F16S=1`"));
-#endif
-      pack_dvb_raw_flags(h, want, &dvb_raw);
-      d->fwd_sliced = h.value_type == SGPU_VAL_F16 && !dvb_raw.empty();
-    }
+    std::vector<uint8_t> dvb_raw;   // DotVByte: the documents that keep the raw record form (a gap too wide for its field)
+    pack_dvb_raw_flags(h, &dvb_raw);
     {
       const char* env_line = hook_raw("SGPU_REC_LINE");
       pack_record_offsets(h, dvb_raw, std::max<uint64_t>(16, env_line ? std::strtoul(env_line, nullptr, 10) : 128) / 16, &rec_off16);
@@ -401,7 +369,7 @@ sgpu_status device_index_upload(const HostIndex& h, int device, DeviceIndex** ou
       (void)hipGetLastError();   // (judge this launch alone: an earlier failed call of the thread leaves its error behind)
       hipLaunchKernelGGL(replicate_records_kernel, dim3(d->n_cu * 8), dim3(256), 0, d->main.stream,
                          (uint8_t*)d->view.fwd, d->view.doc_ref, d->view.post_doc, d->view.post_ref,
-                         (uint64_t)h.n_postings(), (uint32_t)(cw + vb), (uint32_t)(!dvb_raw.empty()), (uint32_t)vb);
+                         (uint64_t)h.n_postings(), (uint32_t)(cw + vb), (uint32_t)(!dvb_raw.empty()));
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipStreamSynchronize(d->main.stream));
     }
@@ -469,9 +437,6 @@ sgpu_status device_index_upload(const HostIndex& h, int device, DeviceIndex** ou
     d->view.dim = (uint32_t)h.dim;
     d->view.n_docs = (uint32_t)h.n_docs;
     d->view.n_bitmap_words = (uint32_t)((h.n_docs + 31) / 32);
-#if defined(SGPU_LAZY_DOCS) && SGPU_LAZY_DOCS
-    d->view.n_postings_lt_2g = h.n_postings() < (1ull << 31) ? 1u : 0u;
-#endif
     // ---- block-count statistics for LDS sizing
     d->list_nb.resize(h.dim);
     d->list_np.resize(h.dim);
@@ -514,7 +479,6 @@ sgpu_status device_index_clone(const DeviceIndex* src, int device, DeviceIndex**
   d->max_nb = src->max_nb;
   d->fwd_block_major = src->fwd_block_major;
   d->value_type = src->value_type;
-  d->fwd_sliced = src->fwd_sliced;
   d->val_scale = src->val_scale;
   auto bail = [&](sgpu_status s) {
     device_index_free(d);
@@ -834,13 +798,6 @@ static sgpu_status make_plan(const DeviceIndex* d, const uint64_t* h_off, const 
     pl.query_cut = query_cut;
     std::vector<uint64_t> keys(nq);
     uint32_t max_nb = 0, dots_cap = 1, max_list_nb = 1;
-    // (test hook SGPU_AFFINITY_CLASSES = n > 0, the bytes experiment of r04 / r05: inside each of n cost classes of the
-    // longest-first order, queries that walk the same FIRST list are queued next to each other - they then run at the
-    // same time on different workgroups and can meet each other's summary rows and records in L2 / the Infinity Cache.
-    // Measured with counters in r05, profiles/r05_bytes_experiments.md: no effect on traffic or time; off.)
-    const uint32_t aff_classes = nq >= 4096 ? hook_u32("SGPU_AFFINITY_CLASSES", 0) : 0;
-    std::vector<uint32_t> first_list;
-    if (aff_classes) first_list.resize(nq);
     {   // serial on purpose (an OpenMP team costs more to wake than this takes): ~60 ns per query for query_cut <= 16
       constexpr uint32_t kSmall = 16;
       std::vector<std::pair<int32_t, uint32_t>> kv;   // (large query_cut only)
@@ -887,7 +844,6 @@ static sgpu_status make_plan(const DeviceIndex* d, const uint64_t* h_off, const 
         }
         const uint32_t c0 = nl ? (query_cut <= kSmall ? sel[0] : kv[0].second) : 0xffffffffu;
         if (nl) max_nb = std::max(max_nb, d->list_nb[c0]);
-        if (!first_list.empty()) first_list[(size_t)q] = c0;
         dots_cap = std::max(dots_cap, nb);
         keys[(size_t)q] = ((uint64_t)(0xffffffffu - (uint32_t)std::min<uint64_t>(np, 0xffffffffull)) << 32) | (uint32_t)q;
       }
@@ -900,12 +856,6 @@ static sgpu_status make_plan(const DeviceIndex* d, const uint64_t* h_off, const 
     // comparator, which was a quarter of the host side of a call). A cost saturates at 2^32 - 1 postings - four times the
     // postings of the whole 8.8M-document collection - beyond which queries simply keep their input order.
     std::sort(keys.begin(), keys.end());
-    if (aff_classes) {
-      const size_t per = ((size_t)nq + aff_classes - 1) / aff_classes;
-      for (size_t c0 = 0; c0 < nq; c0 += per)
-        std::stable_sort(keys.begin() + (long)c0, keys.begin() + (long)std::min<size_t>(nq, c0 + per),
-                         [&](uint64_t x, uint64_t y) { return first_list[(uint32_t)x] < first_list[(uint32_t)y]; });
-    }
     pl.order.resize(2 * (size_t)nq);
     for (uint32_t i = 0; i < nq; ++i) pl.order[i] = (uint32_t)keys[i];
     // LK_HASH seeds: the first multiplier of the family that sends the query's components to distinct slots
@@ -1242,7 +1192,7 @@ static sgpu_status configure(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sg
   a->p.target_list = mode == MODE_DOTS ? sp.query_cut : 0;
   a->p.val_scale = d->val_scale;
   a->p.queue_base = b->staged ? b->queue_base : 0u;
-  a->value_type = d->fwd_sliced ? (uint32_t)kDevValF16Sliced : d->value_type;
+  a->value_type = d->value_type;
   a->ix = d->view;
   a->comp_width = d->comp_width;
   a->block = NT;
@@ -1395,16 +1345,6 @@ static sgpu_status configure(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sg
   if (a->coop.enabled && b->nq <= d->n_cu && !hook_get("SGPU_ITEMS_INIT"))
     a->p.items_init = std::min<uint32_t>(a->p.items_max, std::max<uint32_t>(1, hook_u32("SGPU_COOP_ITEMS_INIT", 128)));
   if (!a->coop.enabled) grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, b->nq));
-  // SGPU_GRID_SPARE=n (a test hook): a device-planned chunk launches n workgroups fewer than the chip holds. The idea - the
-  // plan kernels of the NEXT chunk run in the free slots instead of waiting for this launch's tail - did not survive its
-  // measurements (profiles/r06_entry_point_final.txt): with one free slot per XCD the next chunk's plan still completes
-  // only when this launch's workgroups start to leave (events on the two streams, no profiler attached); with 32 and more
-  // it completes at once, but the next search launch then shares the chip with this one from the start and the call
-  // gets slower (6.15 against 5.95 ms). No slots are left free by default.
-  if (!a->coop.enabled && b->staged && b->device_plan_cut != 0xffffffffu && grid == d->n_cu * (uint32_t)per_cu) {
-    const uint32_t spare = hook_u32("SGPU_GRID_SPARE", 0);
-    if (spare && grid > 2 * spare) grid -= spare;
-  }
   a->grid = grid;
   // A cooperative launch that writes its rows straight into the pinned host arena also tells the host when the LAST
   // query's rows are there (BatchView::done): the call returns them while the launch winds down (helpers leaving, the
@@ -1688,7 +1628,7 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
     const bool hash_family = d->comp_width == 4 && d->value_type == SGPU_VAL_F16 && d->view.dim < (1u << 24);
     uint32_t seen = 0;
     if (nq >= kDevicePlanMinQueries && nq <= kDevicePlanMaxQueries && cut >= 1 && cut <= kDevicePlanCutMax && !sp.first_sorted &&
-        !hash_family && env_u32("SGPU_DEVICE_PLAN", 1) && !hook_u32("SGPU_NO_LPT", 0) && !hook_u32("SGPU_AFFINITY_CLASSES", 0)) {
+        !hash_family && env_u32("SGPU_DEVICE_PLAN", 1) && !hook_u32("SGPU_NO_LPT", 0)) {
       std::lock_guard<std::mutex> lock(d->mu);
       auto it = d->plan_dots_seen.find(cut);
       if (it != d->plan_dots_seen.end()) seen = it->second;

@@ -36,9 +36,6 @@ struct DevView {
   uint64_t knn_total;
   uint32_t knn_dim;
   uint32_t dim, n_docs, n_bitmap_words;
-#if defined(SGPU_LAZY_DOCS) && SGPU_LAZY_DOCS
-  uint32_t n_postings_lt_2g;          // posting indices fit 31 bits (lazy document ids keep one in it_doc next to the visited bit)
-#endif
   // Hashed row directory (r05; u16 components): (posting list, component) -> the list's summary row of that component,
   // so that stage 1 finds a query component's row in ONE trip to HBM instead of the ~12 dependent probes of a binary
   // search over row_comp. Buckets of four 16-byte entries {key = list << 16 | component, first entry (low 32 bits),
@@ -73,9 +70,6 @@ struct BatchView {
                            //   left its writer - the host may hand the rows out while the launch winds down
 };
 
-// LaunchArgs::value_type is SGPU_VAL_* (seismic_hip.h: 0 f16, 1 fixed-u8, 2 DotVByte) or this internal layout of an f16
-// index: binary16 values behind the compressed component stream (search_kernel.inc VT_F16S; chosen at upload)
-enum { kDevValF16Sliced = 3 };
 enum { MODE_SEARCH = 0, MODE_DOTS = 1, MODE_COUNTED = 2 };   // COUNTED: search with the visited bitmap (exact counters)
 // query lookup table in LDS: {32 bits, rank} per 32 ids | one byte per id | bits + 16-bit ranks | hashed {id, weight} entries
 enum { LK_PACKED = 0, LK_DENSE = 1, LK_SPLIT = 2, LK_HASH = 3 };

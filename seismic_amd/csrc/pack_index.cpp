@@ -13,45 +13,31 @@ static inline uint32_t row_dir_bucket_host(uint32_t key, uint32_t n_buckets) {  
   return (uint32_t)(((uint64_t)(uint32_t)(key * 2654435761u) * n_buckets) >> 32);
 }
 
-// ---- compressed component stream (SGPU_VAL_DOTVBYTE: search_kernel.inc VT_DVB; and, since r05, the sliced layout of an
-// f16 index over u16 components: VT_F16S) ---------------------------------------------------------------------------
+// ---- compressed component stream (SGPU_VAL_DOTVBYTE: search_kernel.inc VT_DVB) -----------------------------------
 // A document is stored as 12-byte slices of eight elements - the slice's first component in 16 bits, the gaps of
 // elements 1 .. 3 in 12 bits each, those of elements 4 .. 7 in 11 bits each - when every gap fits its field; otherwise
 // it keeps the raw record form and its refs carry kDvbRawBit in the length field. `raw` is EMPTY for an index that is
 // not sliced at all (every pack_* function below keys on that), else one flag per document.
 static constexpr uint64_t kDvbRawBit = 0x8000;
 static inline uint32_t dvb_gap_limit(uint64_t i) { return (i & 7) <= 3 ? 4096u : 2048u; }   // element i of its slice (i & 7 != 0)
-void pack_dvb_raw_flags(const HostIndex& h, bool f16_slices, std::vector<uint8_t>* out) {
+void pack_dvb_raw_flags(const HostIndex& h, std::vector<uint8_t>* out) {
   std::vector<uint8_t>& raw = *out;
-  const bool sliced = h.value_type == SGPU_VAL_DOTVBYTE || (f16_slices && pack_f16_slices_possible(h));
-  raw.assign(sliced ? h.n_docs : 0, 0);
+  raw.assign(h.value_type == SGPU_VAL_DOTVBYTE ? h.n_docs : 0, 0);
   if (raw.empty()) return;
   const uint16_t* comps = (const uint16_t*)h.fwd_comps.data();
 #pragma omp parallel for schedule(static) num_threads(sgpu::host_threads())
   for (int64_t doc = 0; doc < (int64_t)h.n_docs; ++doc) {
     const uint64_t s0 = h.fwd_offsets[(size_t)doc], s1 = h.fwd_offsets[(size_t)doc + 1];
-    uint8_t r = s1 - s0 > 32767 ? 1 : 0;   // (the raw flag takes bit 15 of the length field; an f16 document that long is stored raw - and cannot be: see pack_f16_slices_possible)
+    uint8_t r = s1 - s0 > 32767 ? 1 : 0;   // (the raw flag takes bit 15 of the length field)
     for (uint64_t i = s0 + 1; i < s1; ++i)
       if (((i - s0) & 7) != 0 && (uint32_t)comps[i] - (uint32_t)comps[i - 1] >= dvb_gap_limit(i - s0)) r = 1;
     raw[(size_t)doc] = r;
   }
 }
-// An f16 index can take the sliced layout when its components are u16 and no document has more than 32767 of them (the
-// raw flag lives in bit 15 of a ref's length field).
-bool pack_f16_slices_possible(const HostIndex& h) {
-  if (h.value_type != SGPU_VAL_F16 || h.comp_width != 2) return false;
-  for (uint64_t d = 0; d < h.n_docs; ++d)
-    if (h.fwd_offsets[d + 1] - h.fwd_offsets[d] > 32767) return false;
-  return true;
-}
 // bytes of a document's record (before the padding to 16)
 static inline uint64_t record_bytes(const HostIndex& h, const std::vector<uint8_t>& raw, uint64_t doc, uint64_t len) {
   const uint64_t npad = (len + 7) & ~7ull;
-  if (!raw.empty() && !raw[doc]) {
-    const uint64_t ns = npad / 8, vb8 = 8ull * h.val_bytes();
-    if (h.val_bytes() == 1) return ns * 20;   // DotVByte (r05): [ns x 16 B: w0 w1 w2 | codes 0-3][ns x 4 B: codes 4-7]
-    return ((ns * 12 + vb8 - 1) & ~(vb8 - 1)) + ns * vb8;   // sliced f16: [ns x 12 B gaps][pad to 16 B][ns x 8 binary16 values]
-  }
+  if (!raw.empty() && !raw[doc]) return npad / 8 * 20;   // DotVByte (r05): [ns x 16 B: w0 w1 w2 | codes 0-3][ns x 4 B: codes 4-7]
   return npad * (h.comp_width + h.val_bytes());
 }
 static inline uint64_t ref_len_field(const HostIndex& h, const std::vector<uint8_t>& raw, uint64_t doc, uint64_t len) {
@@ -93,44 +79,27 @@ void pack_records(const HostIndex& h, const std::vector<uint8_t>& raw, const std
       const uint16_t* comps = (const uint16_t*)h.fwd_comps.data() + s0;
       const uint64_t ns = npad / 8;
       uint32_t* gw = (uint32_t*)rec;
-      const uint64_t vb8 = 8ull * vb;
-      uint8_t* codes = rec + ((ns * 12 + vb8 - 1) & ~(vb8 - 1));   // (sliced f16: the binary16 values behind the 12-byte slices)
-      if (vb == 1) {
-        // DotVByte (r05): a slice's three gap words and its first four codes share ONE aligned 16-byte unit, the other
-        // four codes follow in a dword array: [ns x 16 B][ns x 4 B] (until r04: [ns x 12 B][pad][ns x 8 B])
-        const uint8_t* cd = h.fwd_codes.data() + s0;
-        uint32_t* hi = (uint32_t*)(rec + ns * 16);
-        for (uint64_t sl = 0; sl < ns; ++sl) {
-          uint32_t g[8], cw[2] = {0, 0};
-          g[0] = comps[sl * 8];
-          for (uint64_t i = 1; i < 8; ++i) {
-            const uint64_t e = sl * 8 + i;
-            g[i] = e < len ? (uint32_t)comps[e] - (uint32_t)comps[e - 1] : 0u;
-          }
-          for (uint64_t i = 0; i < 8; ++i) {
-            const uint64_t e = sl * 8 + i;
-            if (e < len) cw[i >> 2] |= (uint32_t)cd[e] << (8 * (i & 3));
-          }
-          gw[4 * sl + 0] = g[0] | (g[1] << 16) | (g[2] << 28);
-          gw[4 * sl + 1] = (g[2] >> 4) | (g[3] << 8) | (g[4] << 20) | (g[5] << 31);
-          gw[4 * sl + 2] = (g[5] >> 1) | (g[6] << 10) | (g[7] << 21);
-          gw[4 * sl + 3] = cw[0];
-          hi[sl] = cw[1];
-        }
-        continue;
-      }
+      // DotVByte (r05): a slice's three gap words and its first four codes share ONE aligned 16-byte unit, the other
+      // four codes follow in a dword array: [ns x 16 B][ns x 4 B] (until r04: [ns x 12 B][pad][ns x 8 B])
+      const uint8_t* cd = h.fwd_codes.data() + s0;
+      uint32_t* hi = (uint32_t*)(rec + ns * 16);
       for (uint64_t sl = 0; sl < ns; ++sl) {
-        uint32_t g[8];
+        uint32_t g[8], cw[2] = {0, 0};
         g[0] = comps[sl * 8];
         for (uint64_t i = 1; i < 8; ++i) {
           const uint64_t e = sl * 8 + i;
           g[i] = e < len ? (uint32_t)comps[e] - (uint32_t)comps[e - 1] : 0u;
         }
-        gw[3 * sl + 0] = g[0] | (g[1] << 16) | (g[2] << 28);
-        gw[3 * sl + 1] = (g[2] >> 4) | (g[3] << 8) | (g[4] << 20) | (g[5] << 31);
-        gw[3 * sl + 2] = (g[5] >> 1) | (g[6] << 10) | (g[7] << 21);
+        for (uint64_t i = 0; i < 8; ++i) {
+          const uint64_t e = sl * 8 + i;
+          if (e < len) cw[i >> 2] |= (uint32_t)cd[e] << (8 * (i & 3));
+        }
+        gw[4 * sl + 0] = g[0] | (g[1] << 16) | (g[2] << 28);
+        gw[4 * sl + 1] = (g[2] >> 4) | (g[3] << 8) | (g[4] << 20) | (g[5] << 31);
+        gw[4 * sl + 2] = (g[5] >> 1) | (g[6] << 10) | (g[7] << 21);
+        gw[4 * sl + 3] = cw[0];
+        hi[sl] = cw[1];
       }
-      std::memcpy(codes, h.fwd_vals.data() + s0, len * 2);
       continue;
     }
     std::memcpy(rec, h.fwd_comps.data() + s0 * cw, len * cw);

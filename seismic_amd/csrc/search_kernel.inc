@@ -790,22 +790,18 @@ SGPU_DEV void visited_mark(uint32_t* bitmap, uint32_t doc) {
 // elements have gap 0 and code 0 (they repeat the last component with value 0: +-0.0 added, exact). A
 // document with a gap that does not fit its field keeps the VT_U8 record form; bit 15 of the ref's length
 // field says which (documents of a DotVByte index have < 32768 components, checked at conversion).
-// VT_F16S (r05): binary16 values behind the SAME compressed component stream - an internal layout of the f16 index (the
-// host index, its file and the boundary still say SGPU_VAL_F16; chosen at upload, device_index.hip): 28 bytes per
-// 8-element slice instead of 32. The stream is lossless and the values are the f16 index's, so the rows are the f16
-// index's bit for bit. Record: [ns x 12 B slices][pad to 16 B][ns x 16 B values]; raw documents keep the VT_F16 record.
-enum { VT_F16 = 0, VT_U8 = 1, VT_DVB = 2, VT_F16S = 3 };
+enum { VT_F16 = 0, VT_U8 = 1, VT_DVB = 2 };
 template <int VT> struct Vt {
-  static constexpr bool sliced = VT == VT_DVB || VT == VT_F16S;   // compressed component stream, raw fallback per document
-  static constexpr bool half = VT == VT_F16 || VT == VT_F16S;     // binary16 values (else fixed-u8 codes)
-  static constexpr int raw = VT == VT_DVB ? VT_U8 : (VT == VT_F16S ? VT_F16 : VT);   // the record form of a raw document
+  static constexpr bool sliced = VT == VT_DVB;   // compressed component stream, raw fallback per document
+  static constexpr bool half = VT == VT_F16;     // binary16 values (else fixed-u8 codes)
+  static constexpr int raw = VT == VT_DVB ? VT_U8 : VT;   // the record form of a raw document
   static constexpr uint32_t vbytes = half ? 16u : 8u;            // value bytes per slice
 };
 template <int VT> struct LenMask { static constexpr uint32_t v = Vt<VT>::sliced ? 0x7fffu : 0xffffu; };
 constexpr uint32_t kRawBit = 0x8000u;   // VT_DVB refs: the record is in the raw (VT_U8) form
 template <typename CT, int VT>
 struct DocChunk {   // 8 consecutive elements of one document, as loaded
-  uint4 c0, c1, v;   // v: 8 binary16 values (16 bytes), or 8 codes in v.x, v.y; sliced (VT_DVB, VT_F16S): the gaps in c0.x, c0.y, c0.z
+  uint4 c0, c1, v;   // v: 8 binary16 values (16 bytes), or 8 codes in v.x, v.y; sliced (VT_DVB): the gaps in c0.x, c0.y, c0.z
 };
 
 template <int VT>
@@ -1257,17 +1253,6 @@ SGPU_DEV void replay_candidates(RegHeap<KR>& heap, const ChunkBufs& cb, const ui
   }
 }
 
-// Lazy document ids (r04, a traffic trim; compiled in with -DSGPU_LAZY_DOCS=1, OFF by default - it measured slower):
-// once the heap is full, a round's items need their document id only if
-// they can change the heap - the handful that score above the round's starting threshold. Phase A then leaves the
-// POSTING INDEX in it_doc instead of loading post_doc for every item (4 bytes per posting from a second stream of
-// mostly partial lines); the lane that collects a candidate remembers it and replaces the index by the document id
-// at the end of phase B (one round trip per wavefront, at the point where it would wait for the barrier anyway).
-constexpr uint32_t kLazyOff = 0xfffffffeu, kLazyNone = 0xffffffffu;
-SGPU_DEV void resolve_lazy_doc(const DevView& ix, const ChunkBufs& cb, uint32_t item) {
-  if (item < kLazyOff) cb.it_doc[item] = ix.post_doc[cb.it_doc[item]];
-}
-
 // Phase B: speculative scoring of the round's items, 16 lanes per document. Phase A sorted the
 // items into two classes by length (ChunkBufs::it_ord): documents of at most 128 elements (one
 // slice of 8 elements per lane; two thirds of a SPLADE-shaped collection) occupy one slot of 8
@@ -1283,10 +1268,7 @@ SGPU_DEV void resolve_lazy_doc(const DevView& ix, const ChunkBufs& cb, uint32_t 
 // for replay_candidates.
 template <typename CT, int LK, int ND, int NS, int VT, bool SC>
 SGPU_DEV void score_class(const Lds& s, const DevView& ix, const ChunkBufs& cb, const uint16_t* list, int dir,
-                              uint32_t n, uint32_t* pull, bool collect, float thr0, uint32_t& spec_docs, uint32_t len_mask,
-                              uint32_t& lazy_item) {
-  // (lazy_item: kLazyOff = the round's items came with their document ids; else the item, if any, this lane has
-  // collected and whose document id is still its POSTING INDEX in it_doc - see resolve_lazy_doc)
+                              uint32_t n, uint32_t* pull, bool collect, float thr0, uint32_t& spec_docs, uint32_t len_mask) {
   // (len_mask: the bits of a ref's low word that hold the length - a VT_DVB index keeps a format flag above them,
   // also on the records this loop scores in the raw VT_U8 form)
   if (n == 0) return;
@@ -1361,10 +1343,6 @@ SGPU_DEV void score_class(const Lds& s, const DevView& ix, const ChunkBufs& cb, 
       if (collect && len[u] != 0 && a > thr0) {
         const uint32_t slot = atomicAdd(&s.st[ST_NCAND], 1u);
         if (slot < kMaxCand) s.st[ST_CAND + slot] = item[u];
-        if (lazy_item != kLazyOff) {   // a second candidate of this lane in one round (rare): settle the first one now
-          resolve_lazy_doc(ix, cb, lazy_item);
-          lazy_item = item[u];
-        }
       }
     }
   };
@@ -1414,10 +1392,9 @@ SGPU_DEV void score_class(const Lds& s, const DevView& ix, const ChunkBufs& cb, 
 #endif
 template <typename CT, int NT, int LK, bool COUNTED, int VT, bool SC>
 SGPU_DEV void score_items_sc(const Lds& s, const DevView& ix, const ChunkBufs& cb, const KParams& p,
-                             uint32_t& spec_docs, bool lazy_docs) {
+                             uint32_t& spec_docs) {
   const bool collect = !COUNTED && s.st[ST_HLEN] == p.k;   // heap full: only scores above the
   const float thr0 = __uint_as_float(s.st[ST_THR]);            // current k-th best can matter
-  uint32_t lazy_item = (lazy_docs && collect) ? kLazyNone : kLazyOff;   // (phase A used the same predicate)
   const uint32_t n_short = s.st[ST_NSHORT] & 0xffffu, n_long = s.st[ST_NSHORT] >> 16;
   constexpr int kShort = sizeof(CT) == 2 ? (Vt<VT>::half ? SGPU_ND_SHORT : SGPU_ND_SHORT_U8) : SGPU_ND_SHORT_U32;
   constexpr int kLong = sizeof(CT) == 2 ? (Vt<VT>::half ? SGPU_ND_LONG : SGPU_ND_LONG_U8) : SGPU_ND_LONG_U32;
@@ -1434,18 +1411,17 @@ SGPU_DEV void score_items_sc(const Lds& s, const DevView& ix, const ChunkBufs& c
   for (int ph = 0; ph < 2; ++ph) {
     if ((ph == 0) == long_first)
       score_class<CT, LK, kLong, 2, VT, SC>(s, ix, cb, cb.it_ord + (p.items_max - 1), -1, n_long, &s.st[ST_PULL_L], collect, thr0,
-                                        spec_docs, kMask, lazy_item);
+                                        spec_docs, kMask);
     else
-      score_class<CT, LK, kShort, 1, VT, SC>(s, ix, cb, cb.it_ord, 1, n_short, &s.st[ST_TMP2], collect, thr0, spec_docs, kMask, lazy_item);
+      score_class<CT, LK, kShort, 1, VT, SC>(s, ix, cb, cb.it_ord, 1, n_short, &s.st[ST_TMP2], collect, thr0, spec_docs, kMask);
   }
-  resolve_lazy_doc(ix, cb, lazy_item);   // the candidate this lane collected, if any: posting index -> document id
 }
 // (the dense lookup table holds scaled or plain bytes, per query: kScaledMaxNnz; one uniform branch per round)
 template <typename CT, int NT, int LK, bool COUNTED, int VT>
 SGPU_DEV void score_items(const Lds& s, const DevView& ix, const ChunkBufs& cb, const KParams& p,
-                          uint32_t& spec_docs, bool lazy_docs) {
-  if (LK == LK_DENSE && uniform_u(s.st[ST_SCALED]) != 0u) score_items_sc<CT, NT, LK, COUNTED, VT, true>(s, ix, cb, p, spec_docs, lazy_docs);
-  else score_items_sc<CT, NT, LK, COUNTED, VT, false>(s, ix, cb, p, spec_docs, lazy_docs);
+                          uint32_t& spec_docs) {
+  if (LK == LK_DENSE && uniform_u(s.st[ST_SCALED]) != 0u) score_items_sc<CT, NT, LK, COUNTED, VT, true>(s, ix, cb, p, spec_docs);
+  else score_items_sc<CT, NT, LK, COUNTED, VT, false>(s, ix, cb, p, spec_docs);
 }
 
 // Phase A's last step: file item i under its length class (wave-aggregated list appends). Items the
@@ -2924,14 +2900,6 @@ __global__ __launch_bounds__(NT, SGPU_WAVES_PER_EU) void seismic_search_kernel(D
             }
             piece_items = n_items;
             // (c) phase A: posting refs (thread per item; + visited bits in the counted pass)
-#ifndef SGPU_LAZY_DOCS
-#define SGPU_LAZY_DOCS 0   // measured r04: bit-identical, ~4 % less HBM traffic for the posting arrays, 1 % SLOWER (5.96 / 5.95 ms
-#endif                     // against 5.91 / 5.88 per 10 000-query launch): off; profiles/r04_lazy_docs.txt
-#if SGPU_LAZY_DOCS
-            const bool lazy_docs = !COUNTED && s.st[ST_HLEN] == p.k && ix.n_postings_lt_2g;
-#else
-            const bool lazy_docs = false;
-#endif
             if (threadIdx.x == 0) {
               s.st[ST_TMP2] = 0;    // phase B's item counters
               s.st[ST_PULL_L] = 0;
@@ -2951,8 +2919,7 @@ __global__ __launch_bounds__(NT, SGPU_WAVES_PER_EU) void seismic_search_kernel(D
               }
               const uint32_t excl = lo ? cb.cb_incl[lo - 1] : 0;
               const uint32_t pidx = cb.cb_p0[lo] + (gi - excl);
-              // (heap full, no visited bitmap: the document id is fetched later, for the candidates only - resolve_lazy_doc)
-              const uint32_t doc = lazy_docs ? pidx : ix.post_doc[pidx];
+              const uint32_t doc = ix.post_doc[pidx];
               const uint64_t ref = ix.post_ref[pidx];
               const uint32_t vis = (COUNTED && visited_test(bitmap, doc)) ? 0x80000000u : 0u;
               cb.it_ref[i] = ref;
@@ -2963,7 +2930,7 @@ __global__ __launch_bounds__(NT, SGPU_WAVES_PER_EU) void seismic_search_kernel(D
             __syncthreads();
             TICK(6);
             // (d) phase B: speculative scoring (score_items)
-            score_items<CT, NT, LK, COUNTED, VT>(s, ix, cb, p, spec_docs, lazy_docs);
+            score_items<CT, NT, LK, COUNTED, VT>(s, ix, cb, p, spec_docs);
             __syncthreads();
             TICK(7);
             // (e) exact replay on wavefront 0
@@ -3036,7 +3003,7 @@ __global__ __launch_bounds__(NT, SGPU_WAVES_PER_EU) void seismic_search_kernel(D
             classify_item<VT>(s.st, cb, p.items_max, i, (uint32_t)ref, !vis);
           }
           __syncthreads();
-          score_items<CT, NT, LK, COUNTED, VT>(s, ix, cb, p, spec_docs, false);   // (refinement items carry document ids)
+          score_items<CT, NT, LK, COUNTED, VT>(s, ix, cb, p, spec_docs);
           __syncthreads();
           if (wave == 0) replay_round<KR, COUNTED>(cb, s, p, n_items, bitmap, decided_blk, true, wc, nullptr, LenMask<VT>::v, true);
           __syncthreads();

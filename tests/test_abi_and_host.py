@@ -428,31 +428,29 @@ def test_chunk_plan_of_a_call_covers_every_query_once():
     """How sgpu_batch_search cuts a call into launches (abi.cpp chunk_jobs / chunk_bounds, through the debug export):
     whatever the sizes, the launches are contiguous, in order, non-empty and cover [0, nq) exactly once."""
     L = ctypes.CDLL(_native.LIB_PATH)
-    L.sgpu_debug_chunk_plan.restype = ctypes.c_uint32
-    L.sgpu_debug_chunk_plan.argtypes = [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_uint32)]
+    L.sgpu_debug_chunk_bounds.restype = ctypes.c_uint32
+    L.sgpu_debug_chunk_bounds.argtypes = [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint32)]
     bounds = (ctypes.c_uint32 * 16)()
     sizes = list(range(0, 70)) + [255, 256, 257, 511, 599, 600, 1199, 1200, 1201, 1250, 1799, 1800, 2399, 2400, 2500, 4095,
                                   4096, 4097, 9999, 10000, 65535, 1000003, 2**31 - 1, 2**32 - 1]
     for nq in sizes:
         for chunk_min, chunk_max in ((600, 4), (2048, 4), (1, 8), (0, 4), (300, 2)):
-            for want_tail, coop_max in ((0, 256), (256, 256), (64, 256), (300, 256), (128, 0)):
-                for lanes in (1, 2, 3, 8):
-                    n = L.sgpu_debug_chunk_plan(nq, chunk_min, chunk_max, want_tail, coop_max, lanes, bounds)
-                    assert 1 <= n <= min(8, lanes), (nq, chunk_min, chunk_max, want_tail, coop_max, lanes, n)
-                    b = [bounds[i] for i in range(2 * n)]
-                    assert b[0] == 0 and b[-1] == nq
-                    for j in range(n):
-                        assert b[2 * j] <= b[2 * j + 1]
-                        if n > 1:
-                            assert b[2 * j] < b[2 * j + 1]          # no empty launch once a call is cut
-                            assert b[2 * j + 1] - b[2 * j] <= nq // 2 + 1 or b[2 * j] == 0   # rebased offsets fit their buffer
-                        if j:
-                            assert b[2 * j] == b[2 * j - 1]
-    # the defaults: 1250 queries -> two launches, 10 000 -> four, 1000 -> one; the cooperative tail only when asked for
-    assert L.sgpu_debug_chunk_plan(1250, 600, 4, 0, 256, 8, bounds) == 2 and bounds[1] == 625
-    assert L.sgpu_debug_chunk_plan(10000, 600, 4, 0, 256, 8, bounds) == 4 and bounds[1] == 2500
-    assert L.sgpu_debug_chunk_plan(1000, 600, 4, 0, 256, 8, bounds) == 1
-    assert L.sgpu_debug_chunk_plan(1000, 600, 4, 256, 256, 8, bounds) == 2 and [bounds[i] for i in range(4)] == [0, 744, 744, 1000]
+            for lanes in (1, 2, 3, 8):
+                n = L.sgpu_debug_chunk_bounds(nq, chunk_min, chunk_max, lanes, bounds)
+                assert 1 <= n <= min(8, lanes), (nq, chunk_min, chunk_max, lanes, n)
+                b = [bounds[i] for i in range(2 * n)]
+                assert b[0] == 0 and b[-1] == nq
+                for j in range(n):
+                    assert b[2 * j] <= b[2 * j + 1]
+                    if n > 1:
+                        assert b[2 * j] < b[2 * j + 1]          # no empty launch once a call is cut
+                        assert b[2 * j + 1] - b[2 * j] <= nq // 2 + 1 or b[2 * j] == 0   # rebased offsets fit their buffer
+                    if j:
+                        assert b[2 * j] == b[2 * j - 1]
+    # the defaults: 1250 queries -> two launches, 10 000 -> four, 1000 -> one
+    assert L.sgpu_debug_chunk_bounds(1250, 600, 4, 8, bounds) == 2 and bounds[1] == 625
+    assert L.sgpu_debug_chunk_bounds(10000, 600, 4, 8, bounds) == 4 and bounds[1] == 2500
+    assert L.sgpu_debug_chunk_bounds(1000, 600, 4, 8, bounds) == 1
 
 
 def test_cpu_quota_of_the_container_caps_the_default_host_team(tmp_path, monkeypatch):
@@ -561,32 +559,6 @@ def test_dotvbyte_records_decode_to_their_documents(tmp_path):
     assert back.desc.value_type == 2 and np.array_equal(orc.desc_arrays(back.desc)["fwd_vals"], a2["fwd_vals"])
     again = dvb.convert(1)   # (kept alive: desc_arrays views the index's own memory)
     assert again.desc.value_type == 1 and np.array_equal(orc.desc_arrays(again.desc)["fwd_vals"], a1["fwd_vals"])
-    # the f16 index itself can take the same component stream in front of its binary16 values (r05: the sliced internal
-    # layout, SGPU_FWD_STREAM=sliced in libraries built WITH_F16S=1; the host-side packing is always there): every record decodes to
-    # its document with the SAME raw / packed decision per document, and the store is smaller than the plain one
-    need_s, need_p = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    assert L.sgpu_debug_pack_forward(f16.h, None, 0, None, ctypes.byref(need_p)) == 0
-    os.environ["SGPU_FWD_STREAM"] = "sliced"
-    try:
-        assert L.sgpu_debug_pack_forward(f16.h, None, 0, None, ctypes.byref(need_s)) == 0
-        assert need_s.value < need_p.value
-        fwd_s = np.zeros(need_s.value + 16, np.uint8)
-        refs_s = np.zeros(d.n_docs, np.uint64)
-        assert L.sgpu_debug_pack_forward(f16.h, fwd_s.ctypes.data_as(ctypes.c_void_p), need_s.value, refs_s.ctypes.data_as(ctypes.c_void_p),
-                                         ctypes.byref(need_s)) == 0
-    finally:
-        del os.environ["SGPU_FWD_STREAM"]
-    O.orc_slices_decode_record.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-    af = orc.desc_arrays(f16.desc)
-    for doc in range(int(d.n_docs)):
-        ref, ref_d = int(refs_s[doc]), int(refs[doc])
-        ln, raw, off16 = ref & 0x7fff, (ref >> 15) & 1, ref >> 16
-        assert (ln, raw) == (ref_d & 0x7fff, (ref_d >> 15) & 1), doc     # same length, same raw / packed decision as the DotVByte index
-        s, e = int(fo[doc]), int(fo[doc + 1])
-        co, vo = np.zeros(max(ln, 1), np.uint16), np.zeros(max(ln, 1), np.uint16)
-        rc = O.orc_slices_decode_record(fwd_s.ctypes.data + off16 * 16, ln, raw, 2, co.ctypes.data_as(ctypes.c_void_p), vo.ctypes.data_as(ctypes.c_void_p))
-        assert rc == 0, (doc, rc)
-        assert np.array_equal(co[:ln], af["fwd_comps"][s:e]) and np.array_equal(vo[:ln], af["fwd_vals"][s:e].view(np.uint16)), doc
     # u32 components have no DotVByte form (the reference's class is u16-only)
     w = _native.NativeIndex.build(4, 70000, *random_dataset(3, 50, 70000))
     with pytest.raises(_native.SeismicHipError) as ei:
