@@ -328,6 +328,21 @@ sgpu_status sgpu_exact_search(const sgpu_index* idx, const uint64_t* q_off,
                               const uint32_t* comps, const float* vals, uint32_t nq,
                               uint32_t k, uint32_t num_threads, float* out_scores,
                               uint64_t* out_doc_ids, uint32_t* out_n);
+/* The same exact search on the device of replica `replica` of an uploaded index: for every query exactly
+ * what sgpu_exact_search returns (out_n, ids and their order, score bits). Scores that are not finite
+ * (NaN, or inf from inf query values) may be ordered differently. Host buffers in and out, nq x k
+ * row-major; slots past out_n[q] are written as zero. Checks, in this order: the queries (SGPU_EINVAL),
+ * k == 0 (SGPU_EINVAL), k > 1024 (SGPU_ELIMIT), index not uploaded or replica out of range
+ * (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays usable for search).
+ * The first call on a replica builds there an "exact file" of the forward index, kept until
+ * sgpu_index_destroy (or a new upload) and not counted by sgpu_index_device_bytes:
+ * 4 bytes per stored component plus 4 x ceil(n_docs / 32768) x (dim + 1) bytes of offsets
+ * (about 4.2 GB for 8.8M documents of 117 components over a 30K vocabulary). Safe to call while other
+ * threads search the same replica: the call has a stream of its own; exact calls on one replica take
+ * turns. */
+sgpu_status sgpu_exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off,
+                                     const uint32_t* comps, const float* vals, uint32_t nq, uint32_t k,
+                                     float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

@@ -72,6 +72,7 @@ def lib():
         L.sgpu_batch_fetch_stats.argtypes = [vp, vp, vp]
         L.sgpu_summary_distances.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.POINTER(C.c_uint32)]
         L.sgpu_exact_search.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.sgpu_exact_search_device.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -302,6 +303,18 @@ class NativeIndex:
         n = np.zeros(max(nq, 1), np.uint32)
         check(lib().sgpu_exact_search(self.h, _p(q_off), _p(comps), _p(vals), nq, k, num_threads, _p(sc),
                                       _p(ids), _p(n)))
+        return sc, ids, n[:nq]
+
+    def exact_search_device(self, q_off, comps, vals, k, replica=0):
+        """exact_search on the device of an uploaded replica: the same results, bit for bit (the first call
+        builds the replica's exact file, kept until the index is destroyed)."""
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        nq = len(q_off) - 1
+        sc = np.zeros((nq, k), np.float32)
+        ids = np.zeros((nq, k), np.uint64)
+        n = np.zeros(max(nq, 1), np.uint32)
+        check(lib().sgpu_exact_search_device(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, k, _p(sc),
+                                             _p(ids), _p(n)))
         return sc, ids, n[:nq]
 
 

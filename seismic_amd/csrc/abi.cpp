@@ -52,6 +52,10 @@ uint32_t coop_trace_dump(DeviceIndex* d, uint64_t* out, uint32_t cap);
 const DeviceIndex* batch_replica(const sgpu_batch* b);
 sgpu_status device_index_set_knn(DeviceIndex* d, const std::vector<uint32_t>& knn, uint32_t knn_dim);
 sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);
+// exact_device.hip
+sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
+                                uint32_t* out_n);
 }  // namespace sgpu
 
 using namespace sgpu;
@@ -137,6 +141,8 @@ sgpu_status sgpu_index_load(const char* path, sgpu_index** out) {
 }
 
 static void drop_replicas(sgpu_index* idx) {
+  for (ExactFile* f : idx->exact) exact_file_free(f);
+  idx->exact.clear();
   for (DeviceIndex* d : idx->replicas) device_index_free(d);
   idx->replicas.clear();
   idx->dev = nullptr;
@@ -642,6 +648,12 @@ sgpu_status sgpu_exact_search(const sgpu_index* idx, const uint64_t* q_off, cons
                               float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n) {
   if (!idx || !q_off || !out_scores || !out_doc_ids || !out_n) return fail(SGPU_EINVAL, "null argument");
   return exact_search_host(idx->host, q_off, comps, vals, nq, k, num_threads, out_scores, out_doc_ids, out_n);
+}
+
+sgpu_status sgpu_exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                     const float* vals, uint32_t nq, uint32_t k, float* out_scores,
+                                     uint64_t* out_doc_ids, uint32_t* out_n) {
+  return exact_search_device(idx, replica, q_off, comps, vals, nq, k, out_scores, out_doc_ids, out_n);
 }
 
 }  // extern "C"

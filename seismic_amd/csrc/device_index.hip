@@ -231,6 +231,7 @@ void device_index_free(DeviceIndex* d) {
 }
 
 uint64_t device_index_bytes(const DeviceIndex* d) { return d ? d->bytes : 0; }
+int device_index_device(const DeviceIndex* d) { return d->device; }
 
 int device_count() {
   int n = 0;

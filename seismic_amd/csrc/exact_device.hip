@@ -1,0 +1,640 @@
+// exact_device.hip — exact top-k over ALL documents on the device (sgpu_exact_search_device).
+//
+// Same contract as exact.cpp, bit for bit: a document's score starts at +0.0f and takes, for each component it
+// shares with the query in ascending component order, score = score + (q * w) with the multiply and the add each
+// rounded once; every document is a candidate (those sharing nothing score +0.0f); the k best by (score desc, id asc).
+//
+// The "exact file", built on a replica at its first exact call and kept until sgpu_index_destroy: the documents are
+// cut into ranges of kRange = 32768 (u16 local ids); its entries are keyed by (range, component), one u32 each:
+// local id in the low 16 bits, the document value in the index's own encoding in the high 16 (f16 bits or a u8
+// code). Offsets: a dense table of n_ranges x (dim + 1) u32 offsets within a range, plus a u64 base per range (the
+// first entry of the range's first document in the forward index: the file holds the forward index's entries in
+// the same number, regrouped).
+//
+// A query is one (query, range) task per workgroup: the range's f32 accumulators live in LDS (128 KiB), the
+// query's segments are streamed in ascending component order with a workgroup barrier between components (a
+// document appears at most once per component, so no two lanes add into one accumulator between two barriers), and
+// the next step's entries are loaded before the barrier. The task's top-k over all the range's accumulators is a
+// radix select on the 48-bit key (ordered score bits, inverted local id): k candidates per task. A second kernel
+// reduces a query's n_ranges x k candidates (64-bit keys: ordered score bits, inverted global id) to its k best.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "host_index.hpp"
+
+namespace sgpu {
+
+// (device_index.hip)
+int device_index_device(const DeviceIndex* d);
+
+namespace {
+
+constexpr uint32_t kRangeBits = 15, kRange = 1u << kRangeBits;   // documents per range (u16 local ids)
+constexpr uint32_t kBS = 1024;        // threads of the accumulate kernel
+constexpr uint32_t kE = 8;            // entries per thread and step
+constexpr uint32_t kGroup = 256;      // query components resolved to segments at a time (LDS)
+constexpr uint32_t kMergeBS = 256;    // threads of the merge kernel
+constexpr uint32_t kMaxK = 1024;
+constexpr uint64_t kCandBytes = 256ull << 20;   // candidate buffer per chunk of queries
+constexpr uint64_t kMaxTable = 1ull << 28;      // dense offset table entries (1 GiB)
+
+__device__ __forceinline__ uint32_t fkey(float x) {   // ascending with the float (NaN aside)
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ float half_bits_to_f32(uint32_t h) {   // exact binary16 -> binary32 (v_cvt_f32_f16)
+  const unsigned short b = (unsigned short)h;
+  _Float16 x;
+  __builtin_memcpy(&x, &b, 2);
+  return (float)x;
+}
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const uint32_t lane = __lane_id();
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// ---- build -----------------------------------------------------------------------------------------------------
+// one wave per document; every (range, component) pair of the forward index counted
+__global__ __launch_bounds__(256) void exact_count_kernel(const uint64_t* __restrict__ fo, const uint8_t* __restrict__ fc,
+                                                          uint32_t cw, uint64_t n_docs, uint64_t dim1, uint32_t* cnt) {
+  const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint64_t d = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; d < n_docs; d += nw) {
+    uint32_t* row = cnt + (d >> kRangeBits) * dim1;
+    for (uint64_t i = fo[d] + lane; i < fo[d + 1]; i += 64) {
+      const uint32_t c = cw == 2 ? (uint32_t)((const uint16_t*)fc)[i] : ((const uint32_t*)fc)[i];
+      atomicAdd(row + c, 1u);
+    }
+  }
+}
+
+// one workgroup per range: exclusive scan of the row's dim + 1 counts (the last is 0: it becomes the range's total),
+// written to off and, as the scatter's cursor, over cnt
+__global__ __launch_bounds__(1024) void exact_scan_kernel(uint32_t* cnt, uint32_t* off, uint64_t dim1) {
+  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t carry_s;
+  uint32_t* c = cnt + (uint64_t)blockIdx.x * dim1;
+  uint32_t* o = off + (uint64_t)blockIdx.x * dim1;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  for (uint64_t base = 0; base < dim1; base += 4 * 1024) {
+    uint32_t v[4], s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint64_t j = base + 4 * tid + i;
+      v[i] = j < dim1 ? c[j] : 0u;
+      s += v[i];
+    }
+    const uint32_t incl = wave_incl_scan(s);
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    uint32_t before = carry_s;
+    for (uint32_t x = 0; x < w; ++x) before += wsum[x];
+    before += incl - s;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint64_t j = base + 4 * tid + i;
+      if (j < dim1) {
+        o[j] = before;
+        c[j] = before;
+      }
+      before += v[i];
+    }
+    __syncthreads();
+    if (tid == 1023) carry_s = before;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void exact_scatter_kernel(const uint64_t* __restrict__ fo, const uint8_t* __restrict__ fc,
+                                                            const uint8_t* __restrict__ fv, uint32_t cw, uint32_t f16,
+                                                            uint64_t n_docs, uint64_t dim1, const uint64_t* __restrict__ rbase,
+                                                            uint32_t* cur, uint32_t* ent) {
+  const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint64_t d = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; d < n_docs; d += nw) {
+    const uint64_t r = d >> kRangeBits;
+    uint32_t* row = cur + r * dim1;
+    uint32_t* dst = ent + rbase[r];
+    const uint32_t local = (uint32_t)(d & (kRange - 1));
+    for (uint64_t i = fo[d] + lane; i < fo[d + 1]; i += 64) {
+      const uint32_t c = cw == 2 ? (uint32_t)((const uint16_t*)fc)[i] : ((const uint32_t*)fc)[i];
+      const uint32_t v = f16 ? (uint32_t)((const uint16_t*)fv)[i] : (uint32_t)fv[i];
+      const uint32_t p = atomicAdd(row + c, 1u);
+      dst[p] = local | (v << 16);
+    }
+  }
+}
+
+// ---- search ----------------------------------------------------------------------------------------------------
+struct AccArgs {
+  const uint32_t* ent;
+  const uint32_t* off;
+  const uint64_t* rbase;
+  uint64_t dim1, n_docs;
+  uint32_t n_ranges, f16;
+  float val_scale;
+  const uint64_t* q_off;   // the whole call's offsets; this chunk's queries are q0 ..
+  const uint32_t* comps;
+  const float* vals;
+  uint32_t q0, nq, k;
+  uint64_t* cand;          // [query of the chunk][range][k]
+};
+
+// One (query, range) task per workgroup and turn of the grid loop.
+__global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
+  __shared__ __attribute__((aligned(16))) float acc[kRange];
+  __shared__ uint32_t s_b[kGroup], s_e[kGroup];
+  __shared__ float s_qv[kGroup];
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_sel[4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint64_t n_tasks = (uint64_t)a.nq * a.n_ranges;
+  for (uint64_t task = blockIdx.x; task < n_tasks; task += gridDim.x) {
+    const uint32_t ql = (uint32_t)(task / a.n_ranges), r = (uint32_t)(task % a.n_ranges);
+    const uint32_t* off = a.off + (uint64_t)r * a.dim1;
+    const uint32_t* ent = a.ent + a.rbase[r];
+    const uint64_t qb = a.q_off[a.q0 + ql], qe = a.q_off[a.q0 + ql + 1];
+    __syncthreads();   // (the previous task's select is done with acc, hist and s_sel)
+    {
+      float4* a4 = (float4*)acc;
+      for (uint32_t i = tid; i < kRange / 4; i += kBS) a4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (uint64_t g0 = qb; g0 < qe; g0 += kGroup) {
+      const uint32_t gn = (uint32_t)min<uint64_t>(kGroup, qe - g0);
+      __syncthreads();   // (zeroing done / the previous group's segments consumed)
+      if (tid < gn) {
+        const uint32_t c = a.comps[g0 + tid];
+        s_b[tid] = off[c];
+        s_e[tid] = off[c + 1];
+        s_qv[tid] = a.vals[g0 + tid];
+      }
+      __syncthreads();
+      uint32_t j = 0;
+      while (j < gn && s_b[j] == s_e[j]) ++j;
+      uint32_t pos = 0;
+      uint32_t cur[kE];
+      if (j < gn) {
+        const uint32_t b = s_b[j], e = s_e[j];
+#pragma unroll
+        for (uint32_t i = 0; i < kE; ++i) {
+          const uint32_t x = b + i * kBS + tid;
+          cur[i] = x < e ? ent[x] : 0xffffffffu;
+        }
+      }
+      while (j < gn) {
+        const float qv = s_qv[j];
+        uint32_t nj = j, npos = pos + kE * kBS;
+        if (s_b[j] + npos >= s_e[j]) {
+          nj = j + 1;
+          while (nj < gn && s_b[nj] == s_e[nj]) ++nj;
+          npos = 0;
+        }
+        uint32_t nxt[kE];
+        if (nj < gn) {   // the next step's entries are in flight while this step adds and waits at the barrier
+          const uint32_t b = s_b[nj] + npos, e = s_e[nj];
+#pragma unroll
+          for (uint32_t i = 0; i < kE; ++i) {
+            const uint32_t x = b + i * kBS + tid;
+            nxt[i] = x < e ? ent[x] : 0xffffffffu;
+          }
+        } else {
+#pragma unroll
+          for (uint32_t i = 0; i < kE; ++i) nxt[i] = 0xffffffffu;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < kE; ++i) {
+          const uint32_t x = cur[i];
+          if (x != 0xffffffffu) {
+            const uint32_t l = x & 0xffffu;
+            const float w = a.f16 ? half_bits_to_f32(x >> 16) : __fmul_rn((float)(x >> 16), a.val_scale);
+            acc[l] = __fadd_rn(acc[l], __fmul_rn(qv, w));
+          }
+        }
+        if (nj != j) __syncthreads();   // every addition of component j before any of the next
+#pragma unroll
+        for (uint32_t i = 0; i < kE; ++i) cur[i] = nxt[i];
+        j = nj;
+        pos = npos;
+      }
+    }
+    __syncthreads();
+
+    // ---- the task's top-k over all its documents: key = fkey(score) << 16 | (0xffff - local), larger is better
+    const uint64_t d0 = (uint64_t)r * kRange;
+    const uint32_t nr = (uint32_t)min<uint64_t>(kRange, a.n_docs - d0);
+    uint64_t* out = a.cand + task * a.k;
+    if (nr <= a.k) {
+      for (uint32_t l = tid; l < a.k; l += kBS)
+        out[l] = l < nr ? ((uint64_t)fkey(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l)) : 0ull;
+      continue;
+    }
+    uint64_t prefix = 0, mask = 0;
+    uint32_t need = a.k;
+    for (int shift = 40; shift >= 0; shift -= 8) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      uint32_t run_bin = 0xffffffffu, run_n = 0;
+      for (uint32_t it = 0; it < kRange / (4 * kBS); ++it) {
+        const uint32_t l0 = it * 4 * kBS + 4 * tid;
+        const float4 v = ((const float4*)acc)[l0 / 4];
+        const float vs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) {
+          const uint32_t l = l0 + e;
+          const uint64_t key = ((uint64_t)fkey(vs[e]) << 16) | (uint64_t)(0xffffu - l);
+          if (l < nr && (key & mask) == prefix) {
+            const uint32_t bin = (uint32_t)(key >> shift) & 255u;
+            if (bin == run_bin) {
+              ++run_n;
+            } else {
+              if (run_n) atomicAdd(&hist[run_bin], run_n);
+              run_bin = bin;
+              run_n = 1;
+            }
+          }
+        }
+      }
+      if (run_n) atomicAdd(&hist[run_bin], run_n);
+      __syncthreads();
+      if (tid < 64) {   // the bin where the running count from the top reaches `need`
+        uint32_t h[4], s = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+          h[i] = hist[255 - 4 * lane - i];
+          s += h[i];
+        }
+        const uint32_t incl = wave_incl_scan(s);
+        uint32_t above = incl - s;
+        if (above < need && need <= incl) {
+#pragma unroll
+          for (uint32_t i = 0; i < 4; ++i) {
+            if (above < need && need <= above + h[i]) {
+              s_sel[0] = 255 - 4 * lane - i;
+              s_sel[1] = need - above;
+              s_sel[2] = h[i];
+            }
+            above += h[i];
+          }
+        }
+        s_sel[3] = 0;
+      }
+      __syncthreads();
+      const uint32_t b = s_sel[0], hb = s_sel[2];
+      need = s_sel[1];
+      prefix |= (uint64_t)b << shift;
+      mask |= (uint64_t)255 << shift;
+      if (hb == need) break;   // the whole bin is taken
+    }
+    // selected: everything above the bin, and the bin (all of it, or its one document once the key is resolved)
+    for (uint32_t it = 0; it < kRange / (4 * kBS); ++it) {
+      const uint32_t l0 = it * 4 * kBS + 4 * tid;
+      const float4 v = ((const float4*)acc)[l0 / 4];
+      const float vs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (uint32_t e = 0; e < 4; ++e) {
+        const uint32_t l = l0 + e;
+        const uint32_t fk = fkey(vs[e]);
+        const uint64_t key = ((uint64_t)fk << 16) | (uint64_t)(0xffffu - l);
+        if (l < nr && (key & mask) >= prefix) {
+          const uint32_t slot = atomicAdd(&s_sel[3], 1u);
+          if (slot < a.k) out[slot] = ((uint64_t)fk << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l));
+        }
+      }
+    }
+  }
+}
+
+// One workgroup per query: the k best of its n_ranges x k candidates (keys unique but for the 0 padding), sorted.
+__global__ __launch_bounds__(kMergeBS) void exact_merge_kernel(const uint64_t* __restrict__ cand, uint32_t n_ranges,
+                                                               uint32_t k, uint32_t out_n, uint32_t q0, float* out_scores,
+                                                               uint64_t* out_ids, uint32_t* out_nq) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_sel[4];
+  __shared__ uint64_t sel[kMaxK];
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint64_t n = (uint64_t)n_ranges * k;
+  const uint64_t* c = cand + (uint64_t)blockIdx.x * n;
+  uint64_t prefix = 0, mask = 0;
+  uint32_t need = out_n;
+  for (int shift = 56; shift >= 0 && need; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    for (uint64_t i = tid; i < n; i += kMergeBS) {
+      const uint64_t key = c[i];
+      if ((key & mask) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {
+      uint32_t h[4], s = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < 4; ++i) {
+        h[i] = hist[255 - 4 * lane - i];
+        s += h[i];
+      }
+      const uint32_t incl = wave_incl_scan(s);
+      uint32_t above = incl - s;
+      if (above < need && need <= incl) {
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+          if (above < need && need <= above + h[i]) {
+            s_sel[0] = 255 - 4 * lane - i;
+            s_sel[1] = need - above;
+            s_sel[2] = h[i];
+          }
+          above += h[i];
+        }
+      }
+      s_sel[3] = 0;
+    }
+    __syncthreads();
+    const uint32_t b = s_sel[0], hb = s_sel[2];
+    need = s_sel[1];
+    prefix |= (uint64_t)b << shift;
+    mask |= (uint64_t)255 << shift;
+    __syncthreads();   // (s_sel read by every thread before the next pass writes it)
+    if (hb == need) break;
+  }
+  uint32_t p2 = 1;
+  while (p2 < out_n) p2 <<= 1;
+  for (uint32_t i = tid; i < p2; i += kMergeBS) sel[i] = 0;
+  if (tid == 0) s_sel[3] = 0;
+  __syncthreads();
+  if (out_n)
+    for (uint64_t i = tid; i < n; i += kMergeBS) {
+      const uint64_t key = c[i];
+      if ((key & mask) >= prefix) {
+        const uint32_t slot = atomicAdd(&s_sel[3], 1u);
+        if (slot < out_n) sel[slot] = key;
+      }
+    }
+  __syncthreads();
+  // bitonic sort, descending
+  for (uint32_t size = 2; size <= p2; size <<= 1)
+    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+      for (uint32_t i = tid; i < p2 / 2; i += kMergeBS) {
+        const uint32_t lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const uint64_t x = sel[lo], y = sel[hi];
+        if ((x < y) == desc) {
+          sel[lo] = y;
+          sel[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  const uint64_t row = (uint64_t)(q0 + blockIdx.x) * k;
+  for (uint32_t i = tid; i < k; i += kMergeBS) {
+    const uint64_t key = i < out_n ? sel[i] : 0ull;
+    out_scores[row + i] = i < out_n ? fkey_inv((uint32_t)(key >> 32)) : 0.0f;
+    out_ids[row + i] = i < out_n ? (uint64_t)(0xffffffffu - (uint32_t)key) : 0ull;
+  }
+  if (tid == 0) out_nq[q0 + blockIdx.x] = out_n;
+}
+
+}  // namespace
+
+#define EX_TRY(expr)                                                                                          \
+  do {                                                                                                        \
+    hipError_t e_ = (expr);                                                                                   \
+    if (e_ != hipSuccess)                                                                                     \
+      return fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+struct ExactFile {
+  int device = -1;
+  uint32_t n_cu = 0;
+  hipStream_t stream = nullptr;
+  uint64_t n_docs = 0, dim = 0;
+  uint32_t n_ranges = 0, f16 = 1;
+  float val_scale = 0.0f;
+  uint32_t* ent = nullptr;
+  uint32_t* off = nullptr;
+  uint64_t* rbase = nullptr;
+  uint64_t bytes = 0;
+  std::mutex mu;   // one exact call at a time on this file (its stream and scratch)
+  // per-call scratch, grown as calls need it
+  void* scratch[6] = {};   // q_off, comps, vals, candidates, scores, ids
+  uint64_t scratch_bytes[6] = {};
+  uint32_t* d_n = nullptr;
+  uint64_t d_n_bytes = 0;
+};
+
+void exact_file_free(ExactFile* f) {
+  if (!f) return;
+  (void)hipSetDevice(f->device);
+  if (f->stream) (void)hipStreamSynchronize(f->stream);
+  for (void* p : {(void*)f->ent, (void*)f->off, (void*)f->rbase, (void*)f->d_n}) if (p) (void)hipFree(p);
+  for (void* p : f->scratch) if (p) (void)hipFree(p);
+  if (f->stream) (void)hipStreamDestroy(f->stream);
+  delete f;
+}
+
+static sgpu_status ex_alloc(void** p, uint64_t bytes) {
+  if (hipMalloc(p, std::max<uint64_t>(bytes, 16)) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail(SGPU_ENOMEM, "out of device memory for exact search (%llu bytes)", (unsigned long long)bytes);
+  }
+  return SGPU_OK;
+}
+
+// Builds the file of `h` on `device` (histogram, scan, scatter on the device, from the uploaded forward arrays).
+static sgpu_status exact_file_build_on(const HostIndex& h, int device, ExactFile* f) {
+  const uint64_t nnz = h.nnz(), n_ranges = (h.n_docs + kRange - 1) / kRange, dim1 = h.dim + 1;
+  if (n_ranges * dim1 > kMaxTable)
+    return fail(SGPU_ELIMIT, "exact search on the device: %llu ranges x %llu components exceed the offset table",
+                (unsigned long long)n_ranges, (unsigned long long)dim1);
+  std::vector<uint64_t> rbase(n_ranges + 1);
+  for (uint64_t r = 0; r <= n_ranges; ++r) rbase[r] = h.fwd_offsets[std::min<uint64_t>(r * kRange, h.n_docs)];
+  for (uint64_t r = 0; r < n_ranges; ++r)
+    if (rbase[r + 1] - rbase[r] > 0xffffffffull)
+      return fail(SGPU_ELIMIT, "exact search on the device: more than 2^32 entries in a range of documents");
+  f->device = device;
+  f->n_docs = h.n_docs;
+  f->dim = h.dim;
+  f->n_ranges = (uint32_t)n_ranges;
+  f->f16 = h.value_type == SGPU_VAL_F16;
+  f->val_scale = h.val_scale;
+  EX_TRY(hipSetDevice(device));
+  int n_cu = 0;
+  EX_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  f->n_cu = (uint32_t)std::max(n_cu, 1);
+  EX_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+  sgpu_status st;
+  const uint64_t table = n_ranges * dim1;
+  if ((st = ex_alloc((void**)&f->ent, nnz * 4)) != SGPU_OK) return st;
+  if ((st = ex_alloc((void**)&f->off, table * 4)) != SGPU_OK) return st;
+  if ((st = ex_alloc((void**)&f->rbase, (n_ranges + 1) * 8)) != SGPU_OK) return st;
+  f->bytes = nnz * 4 + table * 4 + (n_ranges + 1) * 8;
+  // the forward arrays, and the counts (then the scatter's cursor): freed once the file is built
+  void* tmp[4] = {};
+  auto release = [&]() {
+    (void)hipStreamSynchronize(f->stream);
+    for (void* p : tmp) if (p) (void)hipFree(p);
+  };
+  const uint32_t vb = h.val_bytes();
+  if ((st = ex_alloc(&tmp[0], (h.n_docs + 1) * 8)) != SGPU_OK ||
+      (st = ex_alloc(&tmp[1], nnz * h.comp_width)) != SGPU_OK || (st = ex_alloc(&tmp[2], nnz * vb)) != SGPU_OK ||
+      (st = ex_alloc(&tmp[3], table * 4)) != SGPU_OK) {
+    release();
+    return st;
+  }
+  const void* vals = h.value_type == SGPU_VAL_F16 ? (const void*)h.fwd_vals.data() : (const void*)h.fwd_codes.data();
+  hipError_t e = hipMemcpyAsync(tmp[0], h.fwd_offsets.data(), (h.n_docs + 1) * 8, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(tmp[1], h.fwd_comps.data(), nnz * h.comp_width, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(tmp[2], vals, nnz * vb, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(f->rbase, rbase.data(), (n_ranges + 1) * 8, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(tmp[3], 0, table * 4, f->stream);
+  const uint32_t grid = std::max<uint32_t>(1, (uint32_t)std::min<uint64_t>((h.n_docs + 3) / 4, 64ull * f->n_cu));
+  if (e == hipSuccess && h.n_docs) {
+    hipLaunchKernelGGL(exact_count_kernel, dim3(grid), dim3(256), 0, f->stream, (const uint64_t*)tmp[0],
+                       (const uint8_t*)tmp[1], h.comp_width, h.n_docs, dim1, (uint32_t*)tmp[3]);
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(exact_scan_kernel, dim3((uint32_t)n_ranges), dim3(1024), 0, f->stream, (uint32_t*)tmp[3], f->off, dim1);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(exact_scatter_kernel, dim3(grid), dim3(256), 0, f->stream, (const uint64_t*)tmp[0],
+                         (const uint8_t*)tmp[1], (const uint8_t*)tmp[2], h.comp_width, f->f16, h.n_docs, dim1,
+                         (const uint64_t*)f->rbase, (uint32_t*)tmp[3], f->ent);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+  release();
+  if (e != hipSuccess) return fail(SGPU_EDEVICE, "building the exact file failed: %s", hipGetErrorString(e));
+  return SGPU_OK;
+}
+
+static sgpu_status scratch(ExactFile* f, int i, uint64_t bytes) {
+  if (f->scratch_bytes[i] >= bytes && f->scratch[i]) return SGPU_OK;
+  if (f->scratch[i]) {
+    (void)hipStreamSynchronize(f->stream);
+    (void)hipFree(f->scratch[i]);
+    f->scratch[i] = nullptr;
+    f->scratch_bytes[i] = 0;
+  }
+  const sgpu_status st = ex_alloc(&f->scratch[i], bytes);
+  if (st == SGPU_OK) f->scratch_bytes[i] = std::max<uint64_t>(bytes, 16);
+  return st;
+}
+
+static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                             uint32_t k, float* out_scores, uint64_t* out_ids, uint32_t* out_n) {
+  EX_TRY(hipSetDevice(f->device));
+  const uint32_t out_nn = (uint32_t)std::min<uint64_t>(k, f->n_docs);
+  if (f->n_ranges == 0) {   // (no documents: nothing to return)
+    for (uint32_t q = 0; q < nq; ++q) out_n[q] = 0;
+    return SGPU_OK;
+  }
+  const uint64_t qnnz = q_off[nq];
+  const uint64_t per_q = (uint64_t)f->n_ranges * k * 8;
+  const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, kCandBytes / per_q));
+  sgpu_status st;
+  if ((st = scratch(f, 0, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = scratch(f, 1, qnnz * 4)) != SGPU_OK ||
+      (st = scratch(f, 2, qnnz * 4)) != SGPU_OK || (st = scratch(f, 3, (uint64_t)chunk * per_q)) != SGPU_OK ||
+      (st = scratch(f, 4, (uint64_t)nq * k * 4)) != SGPU_OK || (st = scratch(f, 5, (uint64_t)nq * k * 8)) != SGPU_OK)
+    return st;
+  if (f->d_n_bytes < (uint64_t)nq * 4 || !f->d_n) {
+    if (f->d_n) (void)hipFree(f->d_n);
+    f->d_n = nullptr;
+    f->d_n_bytes = 0;
+    if ((st = ex_alloc((void**)&f->d_n, (uint64_t)nq * 4)) != SGPU_OK) return st;
+    f->d_n_bytes = std::max<uint64_t>((uint64_t)nq * 4, 16);
+  }
+  uint64_t* d_qoff = (uint64_t*)f->scratch[0];
+  EX_TRY(hipMemcpyAsync(d_qoff, q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, f->stream));
+  if (qnnz) {
+    EX_TRY(hipMemcpyAsync(f->scratch[1], comps, qnnz * 4, hipMemcpyHostToDevice, f->stream));
+    EX_TRY(hipMemcpyAsync(f->scratch[2], vals, qnnz * 4, hipMemcpyHostToDevice, f->stream));
+  }
+  AccArgs a{};
+  a.ent = f->ent;
+  a.off = f->off;
+  a.rbase = f->rbase;
+  a.dim1 = f->dim + 1;
+  a.n_docs = f->n_docs;
+  a.n_ranges = f->n_ranges;
+  a.f16 = f->f16;
+  a.val_scale = f->val_scale;
+  a.q_off = d_qoff;
+  a.comps = (const uint32_t*)f->scratch[1];
+  a.vals = (const float*)f->scratch[2];
+  a.k = k;
+  a.cand = (uint64_t*)f->scratch[3];
+  for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+    const uint32_t n = std::min(chunk, nq - q0);
+    a.q0 = q0;
+    a.nq = n;
+    const uint64_t tasks = (uint64_t)n * f->n_ranges;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(tasks, f->n_cu);
+    hipLaunchKernelGGL(exact_accumulate_kernel, dim3(grid), dim3(kBS), 0, f->stream, a);
+    EX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(exact_merge_kernel, dim3(n), dim3(kMergeBS), 0, f->stream, (const uint64_t*)a.cand, f->n_ranges,
+                       k, out_nn, q0, (float*)f->scratch[4], (uint64_t*)f->scratch[5], f->d_n);
+    EX_TRY(hipGetLastError());
+  }
+  EX_TRY(hipMemcpyAsync(out_scores, f->scratch[4], (uint64_t)nq * k * 4, hipMemcpyDeviceToHost, f->stream));
+  EX_TRY(hipMemcpyAsync(out_ids, f->scratch[5], (uint64_t)nq * k * 8, hipMemcpyDeviceToHost, f->stream));
+  EX_TRY(hipMemcpyAsync(out_n, f->d_n, (uint64_t)nq * 4, hipMemcpyDeviceToHost, f->stream));
+  EX_TRY(hipStreamSynchronize(f->stream));
+  return SGPU_OK;
+}
+
+sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
+                                uint32_t* out_n) {
+  if (!idx || !q_off || !out_scores || !out_ids || !out_n) return fail(SGPU_EINVAL, "null argument");
+  {
+    uint32_t max_nnz = 0;
+    const sgpu_status vst = validate_queries(idx->host.dim, q_off, comps, vals, nq, &max_nnz);
+    if (vst != SGPU_OK) return vst;
+  }
+  if (k == 0) return fail(SGPU_EINVAL, "k == 0");
+  if (k > kMaxK) return fail(SGPU_ELIMIT, "k = %u exceeds the limit of %u", k, kMaxK);
+  ExactFile* f = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(idx->exact_mu);
+    if (replica >= idx->replicas.size())
+      return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
+    if (idx->exact.size() != idx->replicas.size()) idx->exact.resize(idx->replicas.size(), nullptr);
+    if (!idx->exact[replica]) {
+      ExactFile* nf = new (std::nothrow) ExactFile();
+      if (!nf) return fail(SGPU_ENOMEM, "out of host memory");
+      sgpu_status st;
+      try {
+        st = exact_file_build_on(idx->host, device_index_device(idx->replicas[replica]), nf);
+      } catch (const std::bad_alloc&) {
+        st = fail(SGPU_ENOMEM, "out of host memory");
+      }
+      if (st != SGPU_OK) {
+        const std::string msg = last_error();
+        exact_file_free(nf);
+        last_error() = msg;
+        return st;
+      }
+      idx->exact[replica] = nf;
+    }
+    f = idx->exact[replica];
+  }
+  if (nq == 0) return SGPU_OK;
+  std::lock_guard<std::mutex> lk(f->mu);
+  return exact_run(f, q_off, comps, vals, nq, k, out_scores, out_ids, out_n);
+}
+
+}  // namespace sgpu

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <atomic>
+#include <mutex>
 #include <vector>
 
 #include "common.hpp"
@@ -9,6 +10,7 @@
 namespace sgpu {
 
 struct DeviceIndex;  // search.hip
+struct ExactFile;    // exact_device.hip
 
 struct HostIndex {
   uint32_t comp_width = 2;
@@ -88,6 +90,8 @@ sgpu_status build_host_index(uint32_t comp_width, uint64_t n_docs, uint64_t dim,
 sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const uint32_t* comps,
                               const float* vals, uint32_t nq, uint32_t k, uint32_t num_threads,
                               float* out_scores, uint64_t* out_ids, uint32_t* out_n);
+// exact_device.hip
+void exact_file_free(ExactFile* f);
 
 }  // namespace sgpu
 
@@ -97,4 +101,6 @@ struct sgpu_index {
   std::vector<sgpu::DeviceIndex*> replicas;   // one per device the index was uploaded to
   sgpu::DeviceIndex* dev = nullptr;           // replicas[0] (null before upload)
   std::atomic<uint32_t> next_replica{0};      // calls too small to shard go to the replicas in turn
+  std::vector<sgpu::ExactFile*> exact;        // per replica: the exact file (null until its first exact call)
+  std::mutex exact_mu;                        // its lazy build
 };

@@ -173,6 +173,20 @@ def _resolve(tokens, values, token_map):
     return np.asarray(comps, np.uint32), np.asarray(vals, np.float32)
 
 
+def _resolve_batch(query_components, query_values, token_map, tokens_of):
+    """Queries resolved one by one (_resolve) into one CSR batch."""
+    cs, vs = [], []
+    off = np.zeros(len(query_components) + 1, np.uint64)
+    for i, (qc, qv) in enumerate(zip(query_components, query_values)):
+        c, v = _resolve(tokens_of(qc), np.asarray(qv, np.float32).ravel(), token_map)
+        cs.append(c)
+        vs.append(v)
+        off[i + 1] = off[i] + len(c)
+    comps = np.concatenate(cs) if cs else np.zeros(0, np.uint32)
+    vals = np.concatenate(vs) if vs else np.zeros(0, np.float32)
+    return off, comps, vals
+
+
 def _cfg(n_postings, centroid_fraction, min_cluster_size, summary_energy, max_fraction, doc_cut, num_threads):
     # SGPU_BUILD_DEVICE=<n>: run the clustering step of the build on HIP device n (byte-identical index)
     dev = os.environ.get("SGPU_BUILD_DEVICE", "")
@@ -197,12 +211,14 @@ class _DatasetBase:
         self._ids, self._vecs, self._contents = [], [], []
         self._native = None
         self._tm = None
+        self._on_device = None
 
     def add_document(self, doc_id, tokens, values, content=None):
         self._ids.append(str(doc_id))
         self._vecs.append({str(t): float(v) for t, v in zip(tokens, values)})
         self._contents.append(content)
         self._native = None
+        self._on_device = None
 
     @property
     def len(self):
@@ -215,19 +231,39 @@ class _DatasetBase:
             # exact search only needs the forward index: build with the cheapest valid config
             self._native = _native.NativeIndex.build(self._CW, max(len(self._tm), 1), off, c, v,
                                                      _cfg(1, 1.0, 0, 1.0, 1.0, 1, 0))
+            self._on_device = None
         return self._native
 
-    def search(self, query_id, query_components, query_values, k):
-        """Exact top-k (brute force, host cores) -> [(query_id, score, doc_id)]."""
+    def _exact(self, q_off, comps, vals, k, device, num_threads=0):
+        """device None: the host cores; an int: that GPU (the frozen index is uploaded there once)."""
+        ix = self._freeze()
+        if device is None:
+            return ix.exact_search(q_off, comps, vals, k, num_threads)
+        if self._on_device != int(device):
+            ix.upload(int(device))   # raises if there is no such device
+            self._on_device = int(device)
+        return ix.exact_search_device(q_off, comps, vals, k)
+
+    def search(self, query_id, query_components, query_values, k, device=None):
+        """Exact top-k (brute force; host cores, or the GPU `device`) -> [(query_id, score, doc_id)]."""
         ix = self._freeze()
         c, v = _resolve([str(t) for t in np.asarray(query_components).ravel()],
                         np.asarray(query_values, np.float32).ravel(), self._tm)
-        sc, ids, n = ix.exact_search(np.array([0, len(c)], np.uint64), c, v, k)
+        sc, ids, n = self._exact(np.array([0, len(c)], np.uint64), c, v, k, device)
         return [(str(query_id), float(sc[0, i]), self._ids[int(ids[0, i])]) for i in range(int(n[0]))]
 
-    def batch_search(self, queries_ids, query_components, query_values, k, num_threads=0):
-        return [self.search(q, c, v, k) for q, c, v in zip(np.asarray(queries_ids).ravel(), query_components,
-                                                           query_values)]
+    def batch_search(self, queries_ids, query_components, query_values, k, num_threads=0, device=None):
+        if device is None:
+            return [self.search(q, c, v, k) for q, c, v in zip(np.asarray(queries_ids).ravel(), query_components,
+                                                               query_values)]
+        self._freeze()
+        qids = [str(x) for x in np.asarray(queries_ids).ravel()]
+        off, comps, vals = _resolve_batch(query_components, query_values, self._tm,
+                                          lambda t: [str(x) for x in np.asarray(t).ravel()])
+        sc, ids, n = self._exact(off, comps, vals, k, device)
+        names = self._ids
+        return [[(qids[i], float(sc[i, j]), names[int(ids[i, j])]) for j in range(int(n[i]))]
+                for i in range(len(qids))]
 
 
 class SeismicDataset(_DatasetBase):
@@ -450,6 +486,20 @@ class _IndexBase:
         vals = np.concatenate(vs) if vs else np.zeros(0, np.float32)
         sc, ids, n = self._ix.batch_search(off, comps, vals, k, query_cut, heap_factor, first_sorted=bool(sorted),
                                            n_knn=n_knn)
+        return [self._remap(qids[i], sc[i], ids[i], n[i]) for i in range(len(qids))]
+
+    def batch_exact_search(self, queries_ids, query_components, query_values, k, device=None):
+        """Exact top-k over the index's own documents -> [[(query_id, score, doc_id)]] in input order, the rows of
+        SeismicDataset.batch_search. device None: the host cores; an int: the GPU the index is on."""
+        qids = [str(x) for x in np.asarray(queries_ids).ravel()]
+        off, comps, vals = _resolve_batch(query_components, query_values, self._tm, lambda t: np.asarray(t).astype(str))
+        if device is None:
+            sc, ids, n = self._ix.exact_search(off, comps, vals, k)
+        else:
+            if int(device) != int(self._device):
+                raise ValueError("the index is on device %d, not %d" % (self._device, int(device)))
+            self._ensure_device()
+            sc, ids, n = self._ix.exact_search_device(off, comps, vals, k)
         return [self._remap(qids[i], sc[i], ids[i], n[i]) for i in range(len(qids))]
 
 
