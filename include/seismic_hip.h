@@ -343,6 +343,50 @@ sgpu_status sgpu_exact_search(const sgpu_index* idx, const uint64_t* q_off,
 sgpu_status sgpu_exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off,
                                      const uint32_t* comps, const float* vals, uint32_t nq, uint32_t k,
                                      float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
+/* ---- document filters ----------------------------------------------------
+ * Restrict a search to a set A of allowed document ids (one tenant's documents, a date range, what a caller may see).
+ * No reference counterpart. Contract: filtered search of index I with A returns exactly what unfiltered search returns
+ * on I_A, the index I with every posting of a document outside A deleted from its block (blocks that become empty are
+ * kept; with a kNN graph, every neighbour outside A replaced by 0xffffffff, which the refine step skips) and nothing
+ * else changed - block order, summaries, forward index, knn_dim. Same out_n, ids in the same order, same score bits,
+ * for every parameter, value type and launch shape. The summaries still bound the remaining documents from above, so
+ * pruning stays sound; as with any approximate search, out_n may be below k even when |A| >= k.
+ * Filtered exact search returns the k best documents of A (out_n = min(k, |A|)), host and device bit-identical.
+ *
+ * A filter belongs to the index it was created on: passing it with another index is SGPU_EINVAL. A NULL filter makes
+ * each filtered call exactly its unfiltered counterpart; otherwise, after the check of the filter's index, the
+ * unfiltered call's checks run in their order. Destroy every filter before its index.
+ * On first use on a replica a filter builds there (on the device) its view: its bitmap, the compacted
+ * block_post_start (n_blocks + 1 u32), post_ref (8 B) and post_doc (4 B) of the allowed postings and, with a graph, a
+ * masked copy of it (4 B per entry); sgpu_filter_device_bytes counts them. sgpu_index_upload, sgpu_index_upload_many,
+ * sgpu_index_set_knn and sgpu_index_build_knn invalidate the views: they are rebuilt on their next use. Filtered and
+ * unfiltered calls may run concurrently on one replica; one filter may serve any number of concurrent calls. */
+typedef struct sgpu_filter sgpu_filter;
+/* A = the n ids of doc_ids (repeats allowed; n == 0: the empty set). An id >= n_docs is SGPU_EINVAL (the message
+ * names the first one). Needs no device: works on an index that is not uploaded (host exact search). */
+sgpu_status sgpu_filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
+/* |A| (0 for NULL). */
+uint64_t sgpu_filter_count(const sgpu_filter* filter);
+/* HBM held by the filter's views on all replicas (0 before its first device use). */
+uint64_t sgpu_filter_device_bytes(const sgpu_filter* filter);
+void sgpu_filter_destroy(sgpu_filter* filter);
+/* sgpu_search / sgpu_batch_search restricted to the filter's documents (replicas shard a batch as without one). */
+sgpu_status sgpu_search_filtered(sgpu_index* idx, const uint32_t* comps, const float* vals, uint32_t nnz,
+                                 const sgpu_search_params* params, float* out_scores, uint64_t* out_doc_ids,
+                                 uint32_t* out_n, const sgpu_filter* filter);
+sgpu_status sgpu_batch_search_filtered(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                       uint32_t nq, const sgpu_search_params* params, float* out_scores,
+                                       uint64_t* out_doc_ids, uint32_t* out_n, const sgpu_filter* filter);
+/* sgpu_exact_search / sgpu_exact_search_device over the filter's documents only. */
+sgpu_status sgpu_exact_search_filtered(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps,
+                                       const float* vals, uint32_t nq, uint32_t k, uint32_t num_threads,
+                                       float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n,
+                                       const sgpu_filter* filter);
+sgpu_status sgpu_exact_search_device_filtered(sgpu_index* idx, uint32_t replica, const uint64_t* q_off,
+                                              const uint32_t* comps, const float* vals, uint32_t nq, uint32_t k,
+                                              float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n,
+                                              const sgpu_filter* filter);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

@@ -73,6 +73,19 @@ def lib():
         L.sgpu_summary_distances.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.POINTER(C.c_uint32)]
         L.sgpu_exact_search.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.sgpu_exact_search_device.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.sgpu_filter_create.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
+        L.sgpu_filter_count.argtypes = [vp]
+        L.sgpu_filter_count.restype = C.c_uint64
+        L.sgpu_filter_device_bytes.argtypes = [vp]
+        L.sgpu_filter_device_bytes.restype = C.c_uint64
+        L.sgpu_filter_destroy.argtypes = [vp]
+        L.sgpu_filter_destroy.restype = None
+        L.sgpu_search_filtered.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SearchParams), vp, vp,
+                                           C.POINTER(C.c_uint32), vp]
+        L.sgpu_batch_search_filtered.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(SearchParams), vp, vp, vp, vp]
+        L.sgpu_exact_search_filtered.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        L.sgpu_exact_search_device_filtered.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp,
+                                                        vp]
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -216,6 +229,11 @@ class NativeIndex:
     def device_bytes(self):
         return int(lib().sgpu_index_device_bytes(self.h))
 
+    def make_filter(self, ids):
+        """A document filter (sgpu_filter_create): `ids` are the allowed document ids (repeats allowed), or a boolean
+        mask of length n_docs. Pass it as filter= to search, batch_search, exact_search and exact_search_device."""
+        return NativeFilter(self, ids)
+
     def stream_stats(self):
         """(documents, elements) a DotVByte index keeps in the raw record form; (0, 0) for the other value types."""
         a, b = C.c_uint64(0), C.c_uint64(0)
@@ -235,18 +253,23 @@ class NativeIndex:
             pass
 
     # ---- search ----
-    def search(self, comps, vals, k, query_cut, heap_factor, first_sorted=False, n_knn=0):
+    def search(self, comps, vals, k, query_cut, heap_factor, first_sorted=False, n_knn=0, filter=None):
         comps = np.ascontiguousarray(comps, np.uint32)
         vals = np.ascontiguousarray(vals, np.float32)
         sc = np.zeros(max(k, 1), np.float32)
         ids = np.zeros(max(k, 1), np.uint64)
         n = C.c_uint32(0)
         p = params(k, query_cut, heap_factor, first_sorted, n_knn)
-        check(lib().sgpu_search(self.h, _p(comps), _p(vals), len(comps), C.byref(p), _p(sc), _p(ids),
-                                C.byref(n)))
+        if filter is None:
+            check(lib().sgpu_search(self.h, _p(comps), _p(vals), len(comps), C.byref(p), _p(sc), _p(ids),
+                                    C.byref(n)))
+        else:
+            check(lib().sgpu_search_filtered(self.h, _p(comps), _p(vals), len(comps), C.byref(p), _p(sc), _p(ids),
+                                             C.byref(n), _filter_handle(filter)))
         return sc[: n.value].copy(), ids[: n.value].copy()
 
-    def batch_search(self, q_off, comps, vals, k, query_cut, heap_factor, first_sorted=False, n_knn=0, out=None):
+    def batch_search(self, q_off, comps, vals, k, query_cut, heap_factor, first_sorted=False, n_knn=0, out=None,
+                     filter=None):
         """out: optional (scores f32 [nq, k], ids u64 [nq, k], n u32 [nq]) to receive the rows (no allocation per call)."""
         q_off, comps, vals = _csr(q_off, comps, vals)
         nq = len(q_off) - 1
@@ -260,8 +283,12 @@ class NativeIndex:
             ids = np.zeros((nq, max(k, 1)), np.uint64)
             n = np.zeros(max(nq, 1), np.uint32)
         p = params(k, query_cut, heap_factor, first_sorted, n_knn)
-        check(lib().sgpu_batch_search(self.h, _p(q_off), _p(comps), _p(vals), nq, C.byref(p), _p(sc),
-                                      _p(ids), _p(n)))
+        if filter is None:
+            check(lib().sgpu_batch_search(self.h, _p(q_off), _p(comps), _p(vals), nq, C.byref(p), _p(sc),
+                                          _p(ids), _p(n)))
+        else:
+            check(lib().sgpu_batch_search_filtered(self.h, _p(q_off), _p(comps), _p(vals), nq, C.byref(p), _p(sc),
+                                                   _p(ids), _p(n), _filter_handle(filter)))
         return sc, ids, n[:nq]
 
     def search_sequential(self, q_off, comps, vals, k, query_cut, heap_factor, first_sorted=False, n_knn=0, per_query=False):
@@ -295,17 +322,21 @@ class NativeIndex:
                                            C.byref(n)))
         return out[: n.value].copy()
 
-    def exact_search(self, q_off, comps, vals, k, num_threads=0):
+    def exact_search(self, q_off, comps, vals, k, num_threads=0, filter=None):
         q_off, comps, vals = _csr(q_off, comps, vals)
         nq = len(q_off) - 1
         sc = np.zeros((nq, k), np.float32)
         ids = np.zeros((nq, k), np.uint64)
         n = np.zeros(max(nq, 1), np.uint32)
-        check(lib().sgpu_exact_search(self.h, _p(q_off), _p(comps), _p(vals), nq, k, num_threads, _p(sc),
-                                      _p(ids), _p(n)))
+        if filter is None:
+            check(lib().sgpu_exact_search(self.h, _p(q_off), _p(comps), _p(vals), nq, k, num_threads, _p(sc),
+                                          _p(ids), _p(n)))
+        else:
+            check(lib().sgpu_exact_search_filtered(self.h, _p(q_off), _p(comps), _p(vals), nq, k, num_threads, _p(sc),
+                                                   _p(ids), _p(n), _filter_handle(filter)))
         return sc, ids, n[:nq]
 
-    def exact_search_device(self, q_off, comps, vals, k, replica=0):
+    def exact_search_device(self, q_off, comps, vals, k, replica=0, filter=None):
         """exact_search on the device of an uploaded replica: the same results, bit for bit (the first call
         builds the replica's exact file, kept until the index is destroyed)."""
         q_off, comps, vals = _csr(q_off, comps, vals)
@@ -313,9 +344,66 @@ class NativeIndex:
         sc = np.zeros((nq, k), np.float32)
         ids = np.zeros((nq, k), np.uint64)
         n = np.zeros(max(nq, 1), np.uint32)
-        check(lib().sgpu_exact_search_device(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, k, _p(sc),
-                                             _p(ids), _p(n)))
+        if filter is None:
+            check(lib().sgpu_exact_search_device(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, k, _p(sc),
+                                                 _p(ids), _p(n)))
+        else:
+            check(lib().sgpu_exact_search_device_filtered(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, k,
+                                                          _p(sc), _p(ids), _p(n), _filter_handle(filter)))
         return sc, ids, n[:nq]
+
+
+def _filter_handle(f):
+    if not isinstance(f, NativeFilter):
+        raise TypeError("filter must be a NativeFilter (NativeIndex.make_filter), got %r" % type(f).__name__)
+    if not f.h:
+        raise ValueError("the filter has been closed")
+    return f.h
+
+
+class NativeFilter:
+    """Owns an sgpu_filter handle: a set of allowed document ids of one index. It keeps that index alive (the C ABI
+    wants every filter destroyed before its index)."""
+
+    def __init__(self, index, ids):
+        self.index = index
+        a = np.asarray(ids)
+        if a.dtype == np.bool_:
+            n_docs = int(index.desc.n_docs)
+            if a.ndim != 1 or len(a) != n_docs:
+                raise ValueError("a boolean mask must have one entry per document (%d), got shape %s" % (n_docs, a.shape))
+            a = np.flatnonzero(a)
+        elif a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("document ids must be integers or a boolean mask, got dtype %s" % a.dtype)
+        a = a.ravel()
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xffffffff):
+            bad = a[(a < 0) | (a > 0xffffffff)][0]
+            raise ValueError("document id %d out of range" % int(bad))
+        self._ids = np.ascontiguousarray(a, np.uint32)
+        self.h = C.c_void_p()
+        h = C.c_void_p()
+        check(lib().sgpu_filter_create(index.h, _p(self._ids), len(self._ids), C.byref(h)))
+        self.h = h
+        del self._ids
+
+    @property
+    def count(self):
+        """Number of allowed documents."""
+        return int(lib().sgpu_filter_count(self.h))
+
+    def device_bytes(self):
+        return int(lib().sgpu_filter_device_bytes(self.h))
+
+    def close(self):
+        if self.h:
+            lib().sgpu_filter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceBatch:

@@ -37,7 +37,8 @@ sgpu_status batch_fetch(DeviceIndex* d, Lane* lane, sgpu_batch* b, uint32_t k, f
 sgpu_status batch_fetch_stats(DeviceIndex* d, sgpu_batch* b, uint32_t* out);
 sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
                           const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& sp, sgpu_batch** slot,
-                          uint32_t followed);   // (0: nothing behind this chunk; 1: other calls; 2: the call's own next chunk)
+                          uint32_t followed,    // (0: nothing behind this chunk; 1: other calls; 2: the call's own next chunk)
+                          const FilterRef* flt);
 sgpu_status staged_finish(DeviceIndex* d, Lane* lane, sgpu_batch* b, float* out_scores, uint64_t* out_ids, uint32_t* out_n);
 sgpu_status summary_distances(DeviceIndex* d, const HostIndex& h, uint32_t list, const uint32_t* comps,
                               const float* vals, uint32_t nnz, float* out_dots, uint32_t* out_nb);
@@ -55,7 +56,15 @@ sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);
 // exact_device.hip
 sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
-                                uint32_t* out_n);
+                                uint32_t* out_n, const sgpu_filter* filter);
+// filter.hip
+sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
+const sgpu_index* filter_index(const sgpu_filter* f);
+const uint32_t* filter_host_bits(const sgpu_filter* f);
+uint64_t filter_count(const sgpu_filter* f);
+uint64_t filter_device_bytes(const sgpu_filter* f);
+void filter_destroy(sgpu_filter* f);
+bool filter_build_times(const sgpu_filter* f, uint32_t replica, double* out2);
 }  // namespace sgpu
 
 using namespace sgpu;
@@ -140,6 +149,13 @@ sgpu_status sgpu_index_load(const char* path, sgpu_index** out) {
   return SGPU_OK;
 }
 
+// Moves the index's generation on when it goes out of scope: the filters' views of the device state this call replaces
+// are rebuilt on their next use (filter.hip).
+struct GenerationBump {
+  sgpu_index* idx;
+  ~GenerationBump() { idx->generation.fetch_add(1, std::memory_order_acq_rel); }
+};
+
 static void drop_replicas(sgpu_index* idx) {
   for (ExactFile* f : idx->exact) exact_file_free(f);
   idx->exact.clear();
@@ -150,6 +166,7 @@ static void drop_replicas(sgpu_index* idx) {
 
 sgpu_status sgpu_index_upload_many(sgpu_index* idx, const int32_t* device_ids, uint32_t n) {
   if (!idx || !device_ids || n == 0) return fail(SGPU_EINVAL, "null argument / no device given");
+  GenerationBump bump{idx};
   drop_replicas(idx);
   // replica 0 is packed on the host and copied over PCIe once; the others are copied from it
   // GPU to GPU (hipMemcpyPeer: xGMI on an MI355X node) instead of n more host uploads
@@ -181,6 +198,7 @@ sgpu_status sgpu_index_set_knn(sgpu_index* idx, const uint32_t* neighbours, uint
   if (n_total && knn_dim == 0) return fail(SGPU_EINVAL, "knn_dim == 0 with a non-empty neighbour array");
   for (uint64_t i = 0; i < n_total; ++i)
     if (neighbours[i] >= idx->host.n_docs) return fail(SGPU_EINVAL, "neighbour id >= n_docs");
+  GenerationBump bump{idx};
   try {
     idx->host.knn.assign(neighbours, neighbours + n_total);
   } catch (const std::bad_alloc&) {
@@ -205,6 +223,7 @@ sgpu_status sgpu_index_get_knn(const sgpu_index* idx, const uint32_t** neighbour
 
 sgpu_status sgpu_index_build_knn(sgpu_index* idx, uint32_t nknn) {
   if (!idx) return fail(SGPU_EINVAL, "null argument");
+  GenerationBump bump{idx};
   try {
     sgpu_status st = build_knn_on_device(idx->dev, idx->host, nknn);   // searches run on replica 0
     for (size_t i = 1; st == SGPU_OK && i < idx->replicas.size(); ++i)
@@ -327,9 +346,10 @@ static void chunk_bounds(uint32_t nq, uint32_t n_jobs, uint32_t j, uint32_t* q0,
 // A large shard is cut into up to four chunks on as many lanes (as many as are free): the host side of
 // chunk i+1 (validation, launch plan, staging of the H2D) runs while the GPU searches chunk i, and
 // the workgroups of chunk i+1 fill the CUs that chunk i's tail leaves idle.
+// (flt: the filter of a filtered call and the replica d is, or null)
 static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& params,
-                                float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n) {
+                                float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n, const FilterRef* flt) {
   static const uint32_t chunk_min = [] {
     const char* v = std::getenv("SGPU_CHUNK_MIN");
     // (600 since r03: a 1250-query call - one rank's shard of a 10 000-query batch on eight GPUs - takes 1115 us in two
@@ -400,7 +420,8 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
       qo = off.data();
     }
     st = staged_launch(d, jb.lane, dim, qo, comps ? comps + q_off[jb.q0] : nullptr, vals ? vals + q_off[jb.q0] : nullptr,
-                       jb.q1 - jb.q0, q_base + jb.q0, params, lane_scratch(jb.lane), j + 1 < n_jobs ? 2u : (in_flight.shared ? 1u : 0u));
+                       jb.q1 - jb.q0, q_base + jb.q0, params, lane_scratch(jb.lane), j + 1 < n_jobs ? 2u : (in_flight.shared ? 1u : 0u),
+                       flt);
     if (st == SGPU_OK) ++launched;
     else msg = last_error();
   }
@@ -418,18 +439,27 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
   return st;
 }
 
-sgpu_status sgpu_batch_search(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
-                              uint32_t nq, const sgpu_search_params* params, float* out_scores,
-                              uint64_t* out_doc_ids, uint32_t* out_n) {
+}  // extern "C"
+
+// sgpu_batch_search, and sgpu_batch_search_filtered once its filter is known to be this index's (filter may be null)
+static sgpu_status batch_search(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                uint32_t nq, const sgpu_search_params* params, float* out_scores,
+                                uint64_t* out_doc_ids, uint32_t* out_n, const sgpu_filter* filter) {
   if (!idx || !params || !q_off || !out_scores || !out_doc_ids || !out_n) return fail(SGPU_EINVAL, "null argument");
   if (params->k == 0) return fail(SGPU_EINVAL, "k must be > 0 (KHeap::new asserts, reference src/utils.rs:23)");
   if (idx->replicas.empty()) return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload)");
   if (q_off[nq] && (!comps || !vals)) return fail(SGPU_EINVAL, "null argument");
   const uint32_t n_rep = (uint32_t)idx->replicas.size();
-  if (n_rep == 1) return search_shard(idx->dev, idx->host.dim, q_off, comps, vals, nq, 0, *params, out_scores, out_doc_ids, out_n);
+  if (n_rep == 1) {
+    const FilterRef fr{filter, 0};
+    return search_shard(idx->dev, idx->host.dim, q_off, comps, vals, nq, 0, *params, out_scores, out_doc_ids, out_n,
+                        filter ? &fr : nullptr);
+  }
   if (nq < 2 * n_rep) {   // too small to shard (single queries of a serving loop): the replicas take such calls in turn
-    DeviceIndex* d = idx->replicas[idx->next_replica.fetch_add(1, std::memory_order_relaxed) % n_rep];
-    return search_shard(d, idx->host.dim, q_off, comps, vals, nq, 0, *params, out_scores, out_doc_ids, out_n);
+    const uint32_t r = idx->next_replica.fetch_add(1, std::memory_order_relaxed) % n_rep;
+    const FilterRef fr{filter, r};
+    return search_shard(idx->replicas[r], idx->host.dim, q_off, comps, vals, nq, 0, *params, out_scores, out_doc_ids, out_n,
+                        filter ? &fr : nullptr);
   }
   // Index replicated on several GPUs: contiguous shards of the batch, one host thread per GPU, no
   // collective; results land in input order (the reference's rayon loop over queries,
@@ -453,9 +483,10 @@ sgpu_status sgpu_batch_search(sgpu_index* idx, const uint64_t* q_off, const uint
     auto shard = [&](uint32_t r) {
       const uint32_t q0 = (uint32_t)((uint64_t)nq * r / n_rep), q1 = (uint32_t)((uint64_t)nq * (r + 1) / n_rep);
       try {
+        const FilterRef fr{filter, r};
         sts[r] = search_shard(idx->replicas[r], idx->host.dim, offs[r].data(), comps ? comps + q_off[q0] : nullptr,
                               vals ? vals + q_off[q0] : nullptr, q1 - q0, q0, *params, out_scores + (size_t)q0 * k,
-                              out_doc_ids + (size_t)q0 * k, out_n + q0);
+                              out_doc_ids + (size_t)q0 * k, out_n + q0, filter ? &fr : nullptr);
         if (sts[r] != SGPU_OK) msgs[r] = last_error();
       } catch (const std::exception&) {
         sts[r] = SGPU_ENOMEM;
@@ -483,6 +514,40 @@ sgpu_status sgpu_batch_search(sgpu_index* idx, const uint64_t* q_off, const uint
   }
   return SGPU_OK;
 }
+
+static sgpu_status foreign_filter(const sgpu_index* idx, const sgpu_filter* filter) {
+  return filter && filter_index(filter) != idx ? fail(SGPU_EINVAL, "the filter was created on another index") : SGPU_OK;
+}
+
+extern "C" {
+
+sgpu_status sgpu_batch_search(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                              uint32_t nq, const sgpu_search_params* params, float* out_scores,
+                              uint64_t* out_doc_ids, uint32_t* out_n) {
+  return batch_search(idx, q_off, comps, vals, nq, params, out_scores, out_doc_ids, out_n, nullptr);
+}
+
+sgpu_status sgpu_batch_search_filtered(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                       uint32_t nq, const sgpu_search_params* params, float* out_scores,
+                                       uint64_t* out_doc_ids, uint32_t* out_n, const sgpu_filter* filter) {
+  const sgpu_status st = foreign_filter(idx, filter);
+  if (st != SGPU_OK) return st;
+  return batch_search(idx, q_off, comps, vals, nq, params, out_scores, out_doc_ids, out_n, filter);
+}
+
+sgpu_status sgpu_search_filtered(sgpu_index* idx, const uint32_t* comps, const float* vals, uint32_t nnz,
+                                 const sgpu_search_params* params, float* out_scores, uint64_t* out_doc_ids,
+                                 uint32_t* out_n, const sgpu_filter* filter) {
+  const uint64_t q_off[2] = {0, nnz};
+  return sgpu_batch_search_filtered(idx, q_off, comps, vals, 1, params, out_scores, out_doc_ids, out_n, filter);
+}
+
+sgpu_status sgpu_filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out) {
+  return filter_create(idx, doc_ids, n, out);
+}
+uint64_t sgpu_filter_count(const sgpu_filter* filter) { return filter_count(filter); }
+uint64_t sgpu_filter_device_bytes(const sgpu_filter* filter) { return filter_device_bytes(filter); }
+void sgpu_filter_destroy(sgpu_filter* filter) { filter_destroy(filter); }
 
 sgpu_status sgpu_search(sgpu_index* idx, const uint32_t* comps, const float* vals, uint32_t nnz,
                         const sgpu_search_params* params, float* out_scores, uint64_t* out_doc_ids,
@@ -650,10 +715,40 @@ sgpu_status sgpu_exact_search(const sgpu_index* idx, const uint64_t* q_off, cons
   return exact_search_host(idx->host, q_off, comps, vals, nq, k, num_threads, out_scores, out_doc_ids, out_n);
 }
 
+sgpu_status sgpu_exact_search_filtered(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps,
+                                       const float* vals, uint32_t nq, uint32_t k, uint32_t num_threads,
+                                       float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n,
+                                       const sgpu_filter* filter) {
+  if (!filter) return sgpu_exact_search(idx, q_off, comps, vals, nq, k, num_threads, out_scores, out_doc_ids, out_n);
+  const sgpu_status st = foreign_filter(idx, filter);
+  if (st != SGPU_OK) return st;
+  if (!idx || !q_off || !out_scores || !out_doc_ids || !out_n) return fail(SGPU_EINVAL, "null argument");
+  return exact_search_host(idx->host, q_off, comps, vals, nq, k, num_threads, out_scores, out_doc_ids, out_n,
+                           filter_host_bits(filter));
+}
+
 sgpu_status sgpu_exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                      const float* vals, uint32_t nq, uint32_t k, float* out_scores,
                                      uint64_t* out_doc_ids, uint32_t* out_n) {
-  return exact_search_device(idx, replica, q_off, comps, vals, nq, k, out_scores, out_doc_ids, out_n);
+  return exact_search_device(idx, replica, q_off, comps, vals, nq, k, out_scores, out_doc_ids, out_n, nullptr);
+}
+
+sgpu_status sgpu_exact_search_device_filtered(sgpu_index* idx, uint32_t replica, const uint64_t* q_off,
+                                              const uint32_t* comps, const float* vals, uint32_t nq, uint32_t k,
+                                              float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n,
+                                              const sgpu_filter* filter) {
+  const sgpu_status st = foreign_filter(idx, filter);
+  if (st != SGPU_OK) return st;
+  return exact_search_device(idx, replica, q_off, comps, vals, nq, k, out_scores, out_doc_ids, out_n, filter);
+}
+
+// (not part of the boundary: device and wall milliseconds of the build of the filter's view on `replica`; SGPU_EINVAL
+// before it is built. tools/filter_probe.py)
+sgpu_status sgpu_debug_filter_build_times(const sgpu_filter* filter, uint32_t replica, double* out2) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!filter || !out2) return fail(SGPU_EINVAL, "null argument");
+  if (!filter_build_times(filter, replica, out2)) return fail(SGPU_EINVAL, "the filter has no view on replica %u", replica);
+  return SGPU_OK;
 }
 
 }  // extern "C"

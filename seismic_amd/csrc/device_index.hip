@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "device_types.hpp"
+#include "filter.hpp"
 #include "host_index.hpp"
 
 namespace sgpu {
@@ -232,6 +233,7 @@ void device_index_free(DeviceIndex* d) {
 
 uint64_t device_index_bytes(const DeviceIndex* d) { return d ? d->bytes : 0; }
 int device_index_device(const DeviceIndex* d) { return d->device; }
+const DevView& device_index_view(const DeviceIndex* d) { return d->view; }
 
 int device_count() {
   int n = 0;
@@ -988,8 +990,9 @@ static bool coop_by_size(const DeviceIndex* d, uint32_t nq) {
 }
 
 // Chooses block size, LDS layout and grid for one search pass (caller holds d->mu).
+// (ov: the view to search instead of the replica's own - a filter's, filter.hip; null: the replica's)
 static sgpu_status configure(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sgpu_search_params& sp, uint32_t mode,
-                             LaunchArgs* a) {
+                             LaunchArgs* a, const DevView* ov = nullptr) {
   if (sp.k == 0) return fail(SGPU_EINVAL, "k must be > 0 (KHeap::new asserts, reference src/utils.rs:23)");
   if (sp.k > b->k_max) return fail(SGPU_EINVAL, "k = %u exceeds the batch's k_max = %u", sp.k, b->k_max);
   if (std::isnan(sp.heap_factor)) return fail(SGPU_EINVAL, "heap_factor is NaN");
@@ -1194,7 +1197,7 @@ static sgpu_status configure(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sg
   a->p.val_scale = d->val_scale;
   a->p.queue_base = b->staged ? b->queue_base : 0u;
   a->value_type = d->value_type;
-  a->ix = d->view;
+  a->ix = ov ? *ov : d->view;
   a->comp_width = d->comp_width;
   a->block = NT;
   a->lds_bytes = (uint32_t)o;
@@ -1541,9 +1544,11 @@ static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 // Validates, plans, stages and launches one search of `nq` queries on `lane`: one H2D, the kernel, one
 // D2H, all enqueued; staged_finish waits and hands the rows out. *slot is the lane's recycled batch.
 // (q_base: the index of the first query in the caller's batch, for error messages.)
+// (flt: the filter the chunk searches with - its view on this replica is fetched, built there on first use, once the
+// queries have passed validation; null or flt->f null: unfiltered)
 sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
                           const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& sp, sgpu_batch** slot,
-                          uint32_t followed) {
+                          uint32_t followed, const FilterRef* flt) {
   if (!d) return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload)");
   if (sp.k == 0) return fail(SGPU_EINVAL, "k must be > 0 (KHeap::new asserts, reference src/utils.rs:23)");
   if (sp.k > 1024) return fail(SGPU_ELIMIT, "k = %u exceeds the heap limit of 1024", sp.k);
@@ -1718,13 +1723,26 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
       }
       validated = true;
     }
-    if (b->device_plan_cut != 0xffffffffu && !b->plan_identity) {
-      // order -> the arena's order region; the maxima -> words 1 - 3 of the status block (zeroed by the copy above, they
-      // come back with the rows); the sort keys borrow the output region, which the search kernel overwrites afterwards
-      // (16 bytes per query at least: room for the <= 2 nq keys)
-      HIP_TRY(launch_device_plan(d->view, b->q_off, b->q_comp, b->q_val, nq, cut, (uint64_t*)(b->arena_dev + r_n),
-                                 (uint32_t*)(b->arena_dev + o_status) + 1, b->q_order, lane->stream));
+  }
+  const DevView* view = &d->view;
+  if (flt && flt->f) {   // (the queries are valid: a filtered call fails as the unfiltered one would up to here)
+    const FilterDeviceView* fv = nullptr;
+    st = filter_view(flt->f, flt->replica, &fv);
+    if (st != SGPU_OK) {
+      const std::string msg = last_error();
+      (void)hipStreamSynchronize(lane->stream);
+      last_error() = msg;
+      return st;
     }
+    view = &fv->view;
+    HIP_TRY(hipSetDevice(d->device));
+  }
+  if (!b->direct_in && b->device_plan_cut != 0xffffffffu && !b->plan_identity) {
+    // order -> the arena's order region; the maxima -> words 1 - 3 of the status block (zeroed by the copy above, they
+    // come back with the rows); the sort keys borrow the output region, which the search kernel overwrites afterwards
+    // (16 bytes per query at least: room for the <= 2 nq keys)
+    HIP_TRY(launch_device_plan(*view, b->q_off, b->q_comp, b->q_val, nq, cut, (uint64_t*)(b->arena_dev + r_n),
+                               (uint32_t*)(b->arena_dev + o_status) + 1, b->q_order, lane->stream));
   }
   pc.lap(2);
   // from here on a failure waits for the stream: the lane (and its pinned arena) goes back to the pool
@@ -1732,7 +1750,7 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
   {
     std::lock_guard<std::mutex> lock(d->mu);   // the occupancy cache is shared by the lanes
     LaunchArgs a{};
-    st = configure(d, lane, b, sp, MODE_SEARCH, &a);
+    st = configure(d, lane, b, sp, MODE_SEARCH, &a, view);
     if (st == SGPU_OK) he = launch_search(a);
     if (b->direct_in) {
       if (st == SGPU_OK && he == hipSuccess) lane->queue_pos += nq + a.grid;   // the tickets this launch takes

@@ -21,7 +21,9 @@ namespace sgpu {
 
 sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const uint32_t* comps,
                               const float* vals, uint32_t nq, uint32_t k, uint32_t num_threads,
-                              float* out_scores, uint64_t* out_ids, uint32_t* out_n) {
+                              float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* allow) {
+  // a filter (allow) leaves the other documents out of the inverted file and out of the zero-score fill
+  auto allowed = [allow](uint64_t d) { return !allow || ((allow[d >> 5] >> (d & 31)) & 1u); };
   if (k == 0) return fail(SGPU_EINVAL, "k == 0");
   const uint64_t nnz = ix.nnz();
   {
@@ -54,7 +56,13 @@ sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const 
         uint64_t d0, d1;
         range(t, &d0, &d1);
         uint64_t* c = cur.data() + (size_t)t * ix.dim;
-        for (uint64_t i = ix.fwd_offsets[d0]; i < ix.fwd_offsets[d1]; ++i) c[ix.comp(i)]++;
+        if (!allow) {
+          for (uint64_t i = ix.fwd_offsets[d0]; i < ix.fwd_offsets[d1]; ++i) c[ix.comp(i)]++;
+        } else {
+          for (uint64_t d = d0; d < d1; ++d)
+            if (allowed(d))
+              for (uint64_t i = ix.fwd_offsets[d]; i < ix.fwd_offsets[d + 1]; ++i) c[ix.comp(i)]++;
+        }
       }
       uint64_t run = 0;
       for (uint64_t c = 0; c < ix.dim; ++c) {
@@ -72,7 +80,7 @@ sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const 
         range(t, &d0, &d1);
         uint64_t* c = cur.data() + (size_t)t * ix.dim;
         for (uint64_t d = d0; d < d1; ++d)
-          for (uint64_t i = ix.fwd_offsets[d]; i < ix.fwd_offsets[d + 1]; ++i) {
+          for (uint64_t i = allowed(d) ? ix.fwd_offsets[d] : ix.fwd_offsets[d + 1]; i < ix.fwd_offsets[d + 1]; ++i) {
             const uint64_t p = c[ix.comp(i)]++;
             idoc[p] = (uint32_t)d;
             ival[p] = ix.val(i);
@@ -145,7 +153,7 @@ sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const 
         if (kk < k || !(cand[kk - 1].first > 0.0f)) {
           size_t added = 0;
           for (uint32_t d = 0; d < ix.n_docs && added < k; ++d)
-            if (!seen[d]) {
+            if (!seen[d] && allowed(d)) {
               cand.emplace_back(0.0f, d);
               ++added;
             }

@@ -24,6 +24,7 @@
 #include <new>
 #include <vector>
 
+#include "filter.hpp"
 #include "host_index.hpp"
 
 namespace sgpu {
@@ -152,6 +153,7 @@ struct AccArgs {
   const float* vals;
   uint32_t q0, nq, k;
   uint64_t* cand;          // [query of the chunk][range][k]
+  const uint32_t* bits;    // a filter's allowed set (bit d of word d / 32), or null: every document is a candidate
 };
 
 // One (query, range) task per workgroup and turn of the grid loop.
@@ -161,6 +163,8 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
   __shared__ float s_qv[kGroup];
   __shared__ uint32_t hist[256];
   __shared__ uint32_t s_sel[4];
+  __shared__ uint32_t s_bm[kRange / 32];   // (filtered calls) the range's allowed documents
+  __shared__ uint32_t s_nok;
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint64_t n_tasks = (uint64_t)a.nq * a.n_ranges;
   for (uint64_t task = blockIdx.x; task < n_tasks; task += gridDim.x) {
@@ -237,9 +241,36 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
     const uint64_t d0 = (uint64_t)r * kRange;
     const uint32_t nr = (uint32_t)min<uint64_t>(kRange, a.n_docs - d0);
     uint64_t* out = a.cand + task * a.k;
-    if (nr <= a.k) {
-      for (uint32_t l = tid; l < a.k; l += kBS)
-        out[l] = l < nr ? ((uint64_t)fkey(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l)) : 0ull;
+    // the task's candidates: its documents l < nr, and of those only the allowed ones when a filter is given (the words
+    // past the range's last document are zero). A range may then yield fewer than min(k, nr): the rest of its slots
+    // are 0, below every real key, and the merge takes min(k, |A|) per query.
+    uint32_t n_ok = nr;
+    if (a.bits) {
+      if (tid == 0) s_nok = 0;
+      __syncthreads();
+      const uint32_t n_words = (nr + 31) / 32;
+      uint32_t c = 0;
+      for (uint32_t i = tid; i < kRange / 32; i += kBS) {
+        const uint32_t w = i < n_words ? a.bits[(d0 >> 5) + i] : 0u;
+        s_bm[i] = w;
+        c += __popc(w);
+      }
+      if (c) atomicAdd(&s_nok, c);
+      __syncthreads();
+      n_ok = s_nok;
+    }
+    auto candidate = [&](uint32_t l) { return a.bits ? ((s_bm[l >> 5] >> (l & 31u)) & 1u) != 0 : l < nr; };
+    if (n_ok <= a.k) {
+      if (!a.bits) {
+        for (uint32_t l = tid; l < a.k; l += kBS)
+          out[l] = l < nr ? ((uint64_t)fkey(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l)) : 0ull;
+        continue;
+      }
+      if (tid == 0) s_sel[3] = 0;
+      __syncthreads();
+      for (uint32_t l = tid; l < nr; l += kBS)
+        if (candidate(l)) out[atomicAdd(&s_sel[3], 1u)] = ((uint64_t)fkey(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l));
+      for (uint32_t l = n_ok + tid; l < a.k; l += kBS) out[l] = 0ull;
       continue;
     }
     uint64_t prefix = 0, mask = 0;
@@ -256,7 +287,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
         for (uint32_t e = 0; e < 4; ++e) {
           const uint32_t l = l0 + e;
           const uint64_t key = ((uint64_t)fkey(vs[e]) << 16) | (uint64_t)(0xffffu - l);
-          if (l < nr && (key & mask) == prefix) {
+          if (candidate(l) && (key & mask) == prefix) {
             const uint32_t bin = (uint32_t)(key >> shift) & 255u;
             if (bin == run_bin) {
               ++run_n;
@@ -309,7 +340,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
         const uint32_t l = l0 + e;
         const uint32_t fk = fkey(vs[e]);
         const uint64_t key = ((uint64_t)fk << 16) | (uint64_t)(0xffffu - l);
-        if (l < nr && (key & mask) >= prefix) {
+        if (candidate(l) && (key & mask) >= prefix) {
           const uint32_t slot = atomicAdd(&s_sel[3], 1u);
           if (slot < a.k) out[slot] = ((uint64_t)fk << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l));
         }
@@ -534,10 +565,12 @@ static sgpu_status scratch(ExactFile* f, int i, uint64_t bytes) {
   return st;
 }
 
+// (bits: a filter's allowed set on this device and its size n_allowed, or null)
 static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
-                             uint32_t k, float* out_scores, uint64_t* out_ids, uint32_t* out_n) {
+                             uint32_t k, float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* bits,
+                             uint64_t n_allowed) {
   EX_TRY(hipSetDevice(f->device));
-  const uint32_t out_nn = (uint32_t)std::min<uint64_t>(k, f->n_docs);
+  const uint32_t out_nn = (uint32_t)std::min<uint64_t>(k, bits ? n_allowed : f->n_docs);
   if (f->n_ranges == 0) {   // (no documents: nothing to return)
     for (uint32_t q = 0; q < nq; ++q) out_n[q] = 0;
     return SGPU_OK;
@@ -577,6 +610,7 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
   a.vals = (const float*)f->scratch[2];
   a.k = k;
   a.cand = (uint64_t*)f->scratch[3];
+  a.bits = bits;
   for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t n = std::min(chunk, nq - q0);
     a.q0 = q0;
@@ -598,7 +632,7 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
 
 sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
-                                uint32_t* out_n) {
+                                uint32_t* out_n, const sgpu_filter* filter) {
   if (!idx || !q_off || !out_scores || !out_ids || !out_n) return fail(SGPU_EINVAL, "null argument");
   {
     uint32_t max_nnz = 0;
@@ -632,9 +666,14 @@ sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_
     }
     f = idx->exact[replica];
   }
+  const FilterDeviceView* fv = nullptr;
+  if (filter) {   // (the filter's view on this replica holds its bitmap there)
+    const sgpu_status st = filter_view(filter, replica, &fv);
+    if (st != SGPU_OK) return st;
+  }
   if (nq == 0) return SGPU_OK;
   std::lock_guard<std::mutex> lk(f->mu);
-  return exact_run(f, q_off, comps, vals, nq, k, out_scores, out_ids, out_n);
+  return exact_run(f, q_off, comps, vals, nq, k, out_scores, out_ids, out_n, fv ? fv->bits : nullptr, fv ? fv->count : 0);
 }
 
 }  // namespace sgpu

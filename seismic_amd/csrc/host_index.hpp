@@ -87,11 +87,18 @@ sgpu_status build_host_index(uint32_t comp_width, uint64_t n_docs, uint64_t dim,
                              const void* comps, const float* vals, const sgpu_build_config& cfg,
                              HostIndex* out);
 // exact.cpp
+// (allow: null, or the allowed set as a bitmap - bit d of word d / 32: the other documents are not candidates)
 sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const uint32_t* comps,
                               const float* vals, uint32_t nq, uint32_t k, uint32_t num_threads,
-                              float* out_scores, uint64_t* out_ids, uint32_t* out_n);
+                              float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* allow = nullptr);
 // exact_device.hip
 void exact_file_free(ExactFile* f);
+
+// filter.hip: which filter a launch searches with (f null: none) and on which replica of the index
+struct FilterRef {
+  const sgpu_filter* f;
+  uint32_t replica;
+};
 
 }  // namespace sgpu
 
@@ -103,4 +110,7 @@ struct sgpu_index {
   std::atomic<uint32_t> next_replica{0};      // calls too small to shard go to the replicas in turn
   std::vector<sgpu::ExactFile*> exact;        // per replica: the exact file (null until its first exact call)
   std::mutex exact_mu;                        // its lazy build
+  // bumped by every call that replaces device state a filter's views derive from (upload, upload_many, set_knn,
+  // build_knn): a view built under an older generation is rebuilt on its next use, never dereferenced (filter.hip)
+  std::atomic<uint64_t> generation{0};
 };

@@ -203,6 +203,43 @@ def _no_knn_path(knn_path):
 
 
 # ---------------------------------------------------------------------------
+class SeismicFilter:
+    """A set of allowed documents of one index (make_filter): search, batch_search and batch_exact_search with
+    filter=this look at those documents only. Not in the reference. It keeps its index alive; on the GPU it holds,
+    per device the index is on, the allowed documents' postings (built on first use, see include/seismic_hip.h)."""
+
+    def __init__(self, index, native_filter):
+        self.index = index
+        self._f = native_filter
+
+    @property
+    def count(self):
+        """Number of allowed documents."""
+        return self._f.count
+
+    def device_bytes(self):
+        """HBM the filter holds on the devices (0 before its first GPU search)."""
+        return self._f.device_bytes()
+
+    def close(self):
+        self._f.close()
+
+
+def _native_filter(owner, filter):
+    """filter= of a search call -> the NativeFilter to pass down (None: no filter). A SeismicFilter must be the
+    owner's; anything else is an iterable of ids, made into a filter for this one call."""
+    if filter is None:
+        return None
+    if isinstance(filter, SeismicFilter):
+        if filter.index is not owner:
+            raise ValueError("the filter was made on another index")
+        return filter._f
+    if isinstance(filter, (str, bytes)):
+        raise TypeError("filter= takes a SeismicFilter or an iterable of document ids, not a single id")
+    return owner.make_filter(filter)._f
+
+
+# ---------------------------------------------------------------------------
 class _DatasetBase:
     """SeismicDataset (reference src/pylib/dataset.rs): add_document + exact search."""
     _CW = 2
@@ -449,31 +486,52 @@ class _IndexBase:
         print("\tTotal: %d Bytes" % (fwd + packed + boffs + summ + knn))
         print("\tHBM resident: %d Bytes" % self._ix.device_bytes())
 
+    def _positions(self):
+        if self._doc_pos is None:   # built on first use: doc id -> position
+            self._doc_pos = {d: i for i, d in enumerate(self._doc_ids)}
+        return self._doc_pos
+
     def get_doc_text(self, doc_id):
         if self._contents is None:
             return None
-        if self._doc_pos is None:   # built on first use: doc id -> position
-            self._doc_pos = {d: i for i, d in enumerate(self._doc_ids)}
-        i = self._doc_pos.get(doc_id)
+        i = self._positions().get(doc_id)
         return None if i is None else self._contents[i]
+
+    def make_filter(self, doc_ids):
+        """A SeismicFilter of the documents `doc_ids` (external ids, as the results name them); an unknown id raises
+        KeyError. Pass it as filter= to search, batch_search and batch_exact_search."""
+        pos = self._positions()
+        if isinstance(doc_ids, (str, bytes)):
+            raise TypeError("make_filter takes an iterable of document ids, not a single id")
+        rows = []
+        for d in doc_ids:
+            i = pos.get(str(d))
+            if i is None:
+                raise KeyError(d)
+            rows.append(i)
+        return SeismicFilter(self, self._ix.make_filter(np.asarray(rows, np.int64)))
 
     # ---- search -------------------------------------------------------
     def _remap(self, query_id, sc, ids, n):
         n, q, names = int(n), str(query_id), self._doc_ids
         return [(q, s, names[i]) for s, i in zip(sc[:n].tolist(), ids[:n].tolist())]
 
-    def search(self, query_id, query_components, query_values, k, query_cut, heap_factor, n_knn=0, sorted=True):
-        """-> [(query_id, score, doc_id)], best first (reference src/pylib/mod.rs:490-533)."""
+    def search(self, query_id, query_components, query_values, k, query_cut, heap_factor, n_knn=0, sorted=True,
+               filter=None):
+        """-> [(query_id, score, doc_id)], best first (reference src/pylib/mod.rs:490-533). filter: a SeismicFilter of
+        this index or an iterable of document ids - only those documents can be returned."""
         self._ensure_device()
+        f = _native_filter(self, filter)
         c, v = _resolve(np.asarray(query_components).astype(str), np.asarray(query_values, np.float32), self._tm)
-        sc, ids = self._ix.search(c, v, k, query_cut, heap_factor, first_sorted=bool(sorted), n_knn=n_knn)
+        sc, ids = self._ix.search(c, v, k, query_cut, heap_factor, first_sorted=bool(sorted), n_knn=n_knn, filter=f)
         return self._remap(query_id, sc, ids, len(ids))
 
     def batch_search(self, queries_ids, query_components, query_values, k, query_cut, heap_factor, n_knn=0,
-                     sorted=True, num_threads=0):
+                     sorted=True, num_threads=0, filter=None):
         """-> [[(query_id, score, doc_id)]] in input order (reference src/pylib/mod.rs:572-655).
-        One GPU pass over the whole batch."""
+        One GPU pass over the whole batch. filter: as for search."""
         self._ensure_device()
+        f = _native_filter(self, filter)
         qids = [str(x) for x in np.asarray(queries_ids).ravel()]
         off = np.zeros(len(qids) + 1, np.uint64)
         cs, vs = [], []
@@ -485,21 +543,23 @@ class _IndexBase:
         comps = np.concatenate(cs) if cs else np.zeros(0, np.uint32)
         vals = np.concatenate(vs) if vs else np.zeros(0, np.float32)
         sc, ids, n = self._ix.batch_search(off, comps, vals, k, query_cut, heap_factor, first_sorted=bool(sorted),
-                                           n_knn=n_knn)
+                                           n_knn=n_knn, filter=f)
         return [self._remap(qids[i], sc[i], ids[i], n[i]) for i in range(len(qids))]
 
-    def batch_exact_search(self, queries_ids, query_components, query_values, k, device=None):
+    def batch_exact_search(self, queries_ids, query_components, query_values, k, device=None, filter=None):
         """Exact top-k over the index's own documents -> [[(query_id, score, doc_id)]] in input order, the rows of
-        SeismicDataset.batch_search. device None: the host cores; an int: the GPU the index is on."""
+        SeismicDataset.batch_search. device None: the host cores; an int: the GPU the index is on. filter: as for
+        search (then the k best of the allowed documents, min(k, their number) of them)."""
+        f = _native_filter(self, filter)
         qids = [str(x) for x in np.asarray(queries_ids).ravel()]
         off, comps, vals = _resolve_batch(query_components, query_values, self._tm, lambda t: np.asarray(t).astype(str))
         if device is None:
-            sc, ids, n = self._ix.exact_search(off, comps, vals, k)
+            sc, ids, n = self._ix.exact_search(off, comps, vals, k, filter=f)
         else:
             if int(device) != int(self._device):
                 raise ValueError("the index is on device %d, not %d" % (self._device, int(device)))
             self._ensure_device()
-            sc, ids, n = self._ix.exact_search_device(off, comps, vals, k)
+            sc, ids, n = self._ix.exact_search_device(off, comps, vals, k, filter=f)
         return [self._remap(qids[i], sc[i], ids[i], n[i]) for i in range(len(qids))]
 
 
@@ -589,20 +649,30 @@ class _RawBase:
         except _native.SeismicHipError as e:
             raise IOError(str(e))
 
-    def search(self, query_components, query_values, k, query_cut, heap_factor, n_knn, sorted):
-        """-> [(score, doc_id)] (reference src/pylib/mod.rs:1033-1076)."""
+    def make_filter(self, doc_ids):
+        """A SeismicFilter of the documents `doc_ids` (integer ids, or a boolean mask of length len). Pass it as
+        filter= to search and batch_search."""
+        return SeismicFilter(self, self._ix.make_filter(np.asarray(list(doc_ids) if not isinstance(doc_ids, np.ndarray)
+                                                                   else doc_ids)))
+
+    def search(self, query_components, query_values, k, query_cut, heap_factor, n_knn, sorted, filter=None):
+        """-> [(score, doc_id)] (reference src/pylib/mod.rs:1033-1076). filter: a SeismicFilter of this index or an
+        iterable of document ids - only those documents can be returned."""
         self._ensure_device()
+        f = _native_filter(self, filter)
         sc, ids = self._ix.search(np.asarray(query_components).astype(np.uint32),
                                   np.asarray(query_values, np.float32), k, query_cut, heap_factor,
-                                  first_sorted=bool(sorted), n_knn=n_knn)
+                                  first_sorted=bool(sorted), n_knn=n_knn, filter=f)
         return [(float(s), int(i)) for s, i in zip(sc, ids)]
 
-    def batch_search(self, query_path, k, query_cut, heap_factor, n_knn, sorted, num_threads=0):
-        """queries.bin in the inner format -> [[(score, doc_id)]] in file order (src/pylib/mod.rs:1098-1146)."""
+    def batch_search(self, query_path, k, query_cut, heap_factor, n_knn, sorted, num_threads=0, filter=None):
+        """queries.bin in the inner format -> [[(score, doc_id)]] in file order (src/pylib/mod.rs:1098-1146).
+        filter: as for search."""
         self._ensure_device()
+        f = _native_filter(self, filter)
         off, c, v = read_inner_format(query_path)
         sc, ids, n = self._ix.batch_search(off, c, v, k, query_cut, heap_factor, first_sorted=bool(sorted),
-                                           n_knn=n_knn)
+                                           n_knn=n_knn, filter=f)
         return [[(float(sc[q, i]), int(ids[q, i])) for i in range(int(n[q]))] for q in range(len(off) - 1)]
 
 
