@@ -239,7 +239,7 @@ sgpu_status sgpu_search(sgpu_index* idx, const uint32_t* comps, const float* val
 /* Replaces: SeismicIndexRaw.batch_search (src/pylib/mod.rs:1111-1146) and the
  * per-query loop of SeismicIndex.batch_search (src/pylib/mod.rs:629-652).
  * Queries in CSR form: query q = [q_off[q], q_off[q+1]). Results in input
- * order: out_scores/out_doc_ids are nq x k (row q padded past out_n[q]).
+ * order: out_scores/out_doc_ids are nq x k (slots of row q past out_n[q] are written as zero).
  * Thread safety: sgpu_search / sgpu_batch_search may be called from any number of host threads on one
  * index (the reference's search takes &self and the index is Sync, src/index_traits.rs:106-113). Each
  * call borrows one of a small pool of (stream, recycled device batch) lanes of the replica it runs on,

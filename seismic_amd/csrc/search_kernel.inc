@@ -3018,7 +3018,7 @@ __global__ __launch_bounds__(NT, SGPU_WAVES_PER_EU) void seismic_search_kernel(D
       const uint32_t hl = s.st[ST_HLEN];
       for (uint32_t e = threadIdx.x; e < p.k; e += NT) {
         os[e] = e < hl ? __uint_as_float(s.heap[e]) : 0.0f;
-        oi[e] = e < hl ? (uint64_t)s.heap[KR * 64 + e] : ~0ull;
+        oi[e] = e < hl ? (uint64_t)s.heap[KR * 64 + e] : 0ull;   // (slots past out_n: zero, as sgpu_exact_search_device's)
       }
       if (threadIdx.x == 0) qb.out_n[q] = hl;
       if (COOP && co.enabled && qb.done) {   // (uniform) the rows of this query are in host memory before it counts as finished:
