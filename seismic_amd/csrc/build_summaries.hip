@@ -13,11 +13,9 @@
 // running sums are SEQUENTIAL f32 additions in the reference and stay sequential here (one thread),
 // so the kept set, the minimum, the step and every code are identical to the host builder's; the
 // divisions and roundf are IEEE-correct on the device. Blocks with more entries than the LDS buffers
-// hold (a few per cent) are left to the host.
-//
-// Known difference (documented, not reachable with non-negative weights): the maximum of a component
-// is taken by f32::total_cmp here and by `<` on the host; they differ only when a block holds both
-// +0.0 and -0.0 for one component.
+// hold (a few per cent) are left to the host, and so is every block with a -0.0 document value
+// (builder.cpp marks them): the maximum of a component is taken by f32::total_cmp here and by `<` in
+// the reference, which keeps whichever zero comes first in posting order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -360,6 +360,7 @@ sgpu_status build_host_index(uint32_t comp_width, uint64_t n_docs, uint64_t dim,
     h.fwd_comps.assign((const uint8_t*)comps_in, (const uint8_t*)comps_in + nnz * comp_width);
     h.fwd_vals.resize(nnz);
     std::vector<uint32_t> wide(nnz);
+    std::vector<uint8_t> has_neg_zero(n_docs, 0);   // documents with a -0.0 value (any input in [-2^-25, 0) becomes one)
     std::atomic<int> bad{0};
 #pragma omp parallel for schedule(static) num_threads(nt)
     for (int64_t doc = 0; doc < (int64_t)n_docs; ++doc) {
@@ -371,6 +372,7 @@ sgpu_status build_host_index(uint32_t comp_width, uint64_t n_docs, uint64_t dim,
         if (c >= dim || (i > s && c <= wide[i - 1])) bad = 2;
         if (std::isnan(vals[i])) bad = 3;  // partial_cmp().unwrap() would panic (src/inverted_index.rs:377)
         h.fwd_vals[i] = f32_to_f16_sat(vals[i]);
+        if (h.fwd_vals[i] == 0x8000u) has_neg_zero[(size_t)doc] = 1;
       }
     }
     if (bad == 1) return fail(SGPU_EINVAL, "offsets not monotone or a document has > 65535 components");
@@ -623,7 +625,10 @@ sgpu_status build_host_index(uint32_t comp_width, uint64_t n_docs, uint64_t dim,
     for (uint64_t c = 0; c < dim; ++c) gb_start[c + 1] = gb_start[c] + (outs[c].block_off.empty() ? 0 : outs[c].block_off.size() - 1);
     const uint64_t n_blocks_all = gb_start[dim];
     std::vector<uint64_t> sb_post(n_blocks_all + 1, 0);   // postings of block b: post_flat2[sb_post[b] .. sb_post[b+1])
-    std::vector<uint32_t> sb_entries(n_blocks_all, 0);    // document entries of the block
+    // document entries of the block; 0xffffffff (above every capacity) = left to the host. That is every block with a
+    // -0.0 value: the reference's maximum of a component is taken with `<` (src/posting_list.rs:344-346), under which the
+    // zero met FIRST stays whatever its sign, and the device's sort by total_cmp cannot know the posting order.
+    std::vector<uint32_t> sb_entries(n_blocks_all, 0);
     std::vector<uint32_t>& post2 = post_flat;             // reused: the postings in block order
     DeviceSummaries ds;
     if (on_device) {
@@ -634,9 +639,13 @@ sgpu_status build_host_index(uint32_t comp_width, uint64_t n_docs, uint64_t dim,
         std::copy(o.post.begin(), o.post.end(), post2.begin() + (long)lp_off[(size_t)c]);
         for (uint64_t b = 0; b < nb; ++b) {
           uint64_t e = 0;
-          for (uint32_t t = o.block_off[b]; t < o.block_off[b + 1]; ++t) e += d.off[o.post[t] + 1] - d.off[o.post[t]];
+          bool neg_zero = false;
+          for (uint32_t t = o.block_off[b]; t < o.block_off[b + 1]; ++t) {
+            e += d.off[o.post[t] + 1] - d.off[o.post[t]];
+            neg_zero |= has_neg_zero[o.post[t]] != 0;
+          }
           sb_post[gb_start[(size_t)c] + b + 1] = lp_off[(size_t)c] + o.block_off[b + 1];
-          sb_entries[gb_start[(size_t)c] + b] = (uint32_t)std::min<uint64_t>(e, 0xffffffffu);
+          sb_entries[gb_start[(size_t)c] + b] = neg_zero ? 0xffffffffu : (uint32_t)std::min<uint64_t>(e, 0xffffffffu);
         }
       }
       for (uint64_t c = 0; c < dim; ++c)   // first block of a list starts where the list's postings start

@@ -528,15 +528,19 @@ def make_case(name, n_queries=40):
     return cw, dim, D, _csr(qs), law, dict(cfg)
 
 
+# where binary16 conversion branches (edge_inputs; the `edges` law of tests/build_cases.py)
+EDGE_SPECIAL = np.array([2.0 ** -14, 2.0 ** -15, 3.0e-6, 2.0 ** -24, 2.0 ** -25, 1.5 * 2.0 ** -24, 2.5 * 2.0 ** -24, 1e-9,
+                         1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 1 + 2.0 ** -11 + 2.0 ** -20, 1 + 2.0 ** -11 - 2.0 ** -20,
+                         2048 + 1, 2048 + 3, 65504.0, 65519.9, 65520.0, 70000.0, 3.0e38, 0.0,
+                         -2.0 ** -25, -1 - 2.0 ** -11, -65520.0, -70000.0, -3.0e-6], np.float32)
+
+
 def edge_inputs():
     """A small collection whose values sit where binary16 conversion branches: below the normal range, exactly on
     rounding ties (to even, both ways), at and beyond the largest finite value, zero, both signs."""
     rng = np.random.default_rng(15)
     dim, n_docs = 120, 700
-    special = np.array([2.0 ** -14, 2.0 ** -15, 3.0e-6, 2.0 ** -24, 2.0 ** -25, 1.5 * 2.0 ** -24, 2.5 * 2.0 ** -24, 1e-9,
-                        1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 1 + 2.0 ** -11 + 2.0 ** -20, 1 + 2.0 ** -11 - 2.0 ** -20,
-                        2048 + 1, 2048 + 3, 65504.0, 65519.9, 65520.0, 70000.0, 3.0e38, 0.0,
-                        -2.0 ** -25, -1 - 2.0 ** -11, -65520.0, -70000.0, -3.0e-6], np.float32)
+    special = EDGE_SPECIAL
     docs = []
     for d in range(n_docs):
         c = _components(rng, int(rng.integers(1, 25)), dim)

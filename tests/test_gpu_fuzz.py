@@ -7,6 +7,7 @@ import pytest
 import orc
 from seismic_amd import _native
 from seismic_amd._abi import BuildConfig
+from util import desc_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +40,31 @@ VALUE_LAWS = {
 }
 
 
+def _collection(seed, law):
+    """The seed's documents and build configuration (and the generator, for what the caller draws next)."""
+    rng = np.random.default_rng(1000 + seed)
+    values = VALUE_LAWS[law]
+    cw = 4 if seed % 5 == 4 else 2
+    dim = int(rng.choice([24, 100, 700, 3000])) if cw == 2 else int(rng.choice([70000, 150000]))
+    n_docs = int(rng.integers(60, 2500))
+    docs = _dataset(rng, n_docs, dim, 1, int(rng.choice([8, 40, 200, 400])), values)
+    cfg = dict(n_postings=int(rng.choice([1, 3, 20, 200])), centroid_fraction=float(rng.choice([0.02, 0.1, 0.3, 0.6])),
+               summary_energy=float(rng.choice([0.2, 0.5, 0.9, 1.0])), max_fraction=float(rng.choice([1.0, 1.5, 6.0])),
+               min_cluster_size=int(rng.integers(0, 6)), doc_cut=int(rng.choice([1, 5, 15])))
+    return rng, values, cw, dim, docs, cfg
+
+
+@pytest.mark.parametrize("law", ["exp", "ties", "signed"])
+@pytest.mark.parametrize("seed", range(14, 26))
+def test_device_build_laws(seed, law):
+    """The device-assisted build of the differential seeds' collections under every value law (test_differential builds
+    on the device only where the law is "exp"): byte-identical to the host builder's index."""
+    _, _, cw, dim, docs, cfg = _collection(seed, law)
+    host = _native.NativeIndex.build(cw, dim, *docs, BuildConfig.defaults(**cfg))
+    dev = _native.NativeIndex.build(cw, dim, *docs, BuildConfig.defaults(use_device=1, **cfg))
+    desc_equal(host.desc, dev.desc)
+
+
 # (launches of 30 queries are cooperative ones by default - the round loop; "plain" switches that variant off, so the
 # same seeds run the plain variants: stage 2 as a stream, 1024-thread workgroups on even seeds, 512 on odd ones)
 @pytest.mark.parametrize("variant", ["default", "plain"])
@@ -55,19 +81,15 @@ def test_differential(seed, variant, monkeypatch):
         monkeypatch.setenv("SGPU_DOTS_CAP", "1")
     if seed >= 14 and seed % 4 == 2:
         monkeypatch.setenv("SGPU_FWD_LAYOUT", "doc")
-    rng = np.random.default_rng(1000 + seed)
     law = ["exp", "ties", "signed"][seed % 3]
-    values = VALUE_LAWS[law]
-    cw = 4 if seed % 5 == 4 else 2
-    dim = int(rng.choice([24, 100, 700, 3000])) if cw == 2 else int(rng.choice([70000, 150000]))
-    n_docs = int(rng.integers(60, 2500))
-    off, comps, vals = _dataset(rng, n_docs, dim, 1, int(rng.choice([8, 40, 200, 400])), values)
-    cfg = dict(n_postings=int(rng.choice([1, 3, 20, 200])), centroid_fraction=float(rng.choice([0.02, 0.1, 0.3, 0.6])),
-               summary_energy=float(rng.choice([0.2, 0.5, 0.9, 1.0])), max_fraction=float(rng.choice([1.0, 1.5, 6.0])),
-               min_cluster_size=int(rng.integers(0, 6)), doc_cut=int(rng.choice([1, 5, 15])))
+    rng, values, cw, dim, (off, comps, vals), cfg = _collection(seed, law)
     if seed >= 14 and seed % 3 == 0:
         cfg["use_device"] = 1
     ix = _native.NativeIndex.build(cw, dim, off, comps, vals, BuildConfig.defaults(**cfg))
+    if cfg.get("use_device") == 1:   # the index searched below is the host builder's, bit for bit
+        host = _native.NativeIndex.build(cw, dim, off, comps, vals, BuildConfig.defaults(**dict(cfg, use_device=0)))
+        desc_equal(host.desc, ix.desc)
+        del host
     if seed >= 14 and seed % 2 == 0:
         # fixed-u8 document values (negative weights quantise to 0), u16 and u32 components; every other such seed with
         # u16 components also compresses the component stream (DotVByte forward index: lossless, same results)

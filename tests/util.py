@@ -32,9 +32,55 @@ def random_queries(seed, nq, dim, nnz_lo=3, nnz_hi=30):
     return orc.csr(vecs)
 
 
-def desc_equal(a, b):
+_SCALARS = ("comp_width", "n_docs", "dim", "nnz", "n_blocks", "n_postings", "n_rows", "n_entries")
+# arrays whose elements belong to one block (desc_diff names it and its postings)
+_BLOCK_LEVEL = ("block_post_start", "blk_min", "blk_quant", "post_doc")
+
+
+def _owner(starts, i):
+    """Index of the range [starts[j], starts[j+1]) that holds i (the last one that starts at or before it)."""
+    return int(np.searchsorted(np.asarray(starts).astype(np.int64), i, side="right") - 1)
+
+
+def desc_diff(a, b):
+    """None where the two descriptors are bit-identical; otherwise a sentence naming the first differing array (in the
+    descriptor's order), the list the element belongs to and, for block-level arrays, the global block, its posting
+    range and the two values."""
+    for f in _SCALARS:
+        if getattr(a, f) != getattr(b, f):
+            return "%s: %d != %d" % (f, getattr(a, f), getattr(b, f))
     A, B = orc.desc_arrays(a), orc.desc_arrays(b)
-    for f in ("comp_width", "n_docs", "dim", "nnz", "n_blocks", "n_postings", "n_rows", "n_entries"):
-        assert getattr(a, f) == getattr(b, f), f
     for k in A:
-        assert np.array_equal(A[k].view(np.uint8), B[k].view(np.uint8)), k
+        x, y = A[k], B[k]
+        if x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8)):
+            continue
+        if x.shape != y.shape:
+            return "%s: %d != %d elements" % (k, len(x), len(y))
+        xb, yb = x.view("u%d" % x.dtype.itemsize), y.view("u%d" % y.dtype.itemsize)
+        i = int(np.flatnonzero(xb != yb)[0])
+        what = "%s[%d]: %r (0x%x) != %r (0x%x)" % (k, i, x[i].item(), int(xb[i]), y[i].item(), int(yb[i]))
+        lbs, bps = A["list_block_start"], A["block_post_start"]
+        if k in ("fwd_offsets", "list_block_start", "list_row_start"):
+            return what + (" (document %d)" % i if k == "fwd_offsets" else " (list %d)" % min(i, a.dim - 1))
+        if k in ("fwd_comps", "fwd_vals"):
+            return what + " (document %d)" % _owner(A["fwd_offsets"], i)
+        if k in _BLOCK_LEVEL:
+            blk = _owner(bps, i) if k == "post_doc" else min(i, a.n_blocks - 1)
+            return what + " (list %d, block %d = its block %d, postings [%d, %d) of a: %s; of b: %s)" % (
+                _owner(lbs, blk), blk, blk - int(lbs[_owner(lbs, blk)]), bps[blk], bps[blk + 1],
+                A["post_doc"][int(bps[blk]): int(bps[blk + 1])][:12].tolist(),
+                B["post_doc"][int(B["block_post_start"][blk]): int(B["block_post_start"][blk + 1])][:12].tolist())
+        row = _owner(A["row_ptr"], i) if k in ("sum_bid", "sum_code") else min(i, a.n_rows - 1)
+        lst = _owner(A["list_row_start"], row)
+        what += " (list %d, row %d = component %d" % (lst, row, A["row_comp"][row])
+        if k in ("sum_bid", "sum_code"):
+            blk = int(lbs[lst]) + int(A["sum_bid"][i])
+            what += ", a's block %d: postings [%d, %d), blk_min %r, blk_quant %r" % (
+                blk, bps[blk], bps[blk + 1], A["blk_min"][blk].item(), A["blk_quant"][blk].item())
+        return what + ")"
+    return None
+
+
+def desc_equal(a, b):
+    diff = desc_diff(a, b)
+    assert diff is None, diff
