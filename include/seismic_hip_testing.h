@@ -14,6 +14,13 @@ extern "C" {
 uint32_t sgpu_debug_host_threads(void);
 /* how sgpu_batch_search cuts a call of nq queries into launches: bounds[2j], bounds[2j+1] = queries [q0, q1) of launch j */
 uint32_t sgpu_debug_chunk_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t lanes_free, uint32_t* bounds);
+/* the same for a call of any size (more than 8 x 16384 queries are served in segments, one after the other): every launch
+ * of the call in order, at most cap of them written; first_pm: the first chunk's share in per mille (0: equal chunks) */
+uint32_t sgpu_debug_call_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t lanes_free, uint32_t first_pm,
+                                uint32_t* bounds, uint32_t cap);
+/* the last chunk pool lane `lane` (0 ... 7) of replica 0 served: info4 = {queries, first query in the call's batch, planned by
+ * 0 the host / 1 the device / 2 nobody (input order), query_cut}; host-planned: its launch order as it went down. 0: none */
+uint32_t sgpu_debug_lane_chunk(sgpu_index* idx, uint32_t lane, uint32_t* info4, uint32_t* order_out, uint32_t cap);
 /* the forward store as sgpu_index_upload packs it (document-major records) and every document's ref */
 sgpu_status sgpu_debug_pack_forward(const sgpu_index* idx, uint8_t* out_fwd, uint64_t cap, uint64_t* out_doc_ref,
                                     uint64_t* out_bytes);

@@ -38,18 +38,19 @@ sgpu_status batch_fetch_stats(DeviceIndex* d, sgpu_batch* b, uint32_t* out);
 sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
                           const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& sp, sgpu_batch** slot,
                           uint32_t followed,    // (0: nothing behind this chunk; 1: other calls; 2: the call's own next chunk)
-                          const FilterRef* flt);
+                          const FilterRef* flt, uint32_t chunk);   // (chunk: which launch of its call, 0 = the first or only one)
 sgpu_status staged_finish(DeviceIndex* d, Lane* lane, sgpu_batch* b, float* out_scores, uint64_t* out_ids, uint32_t* out_n);
 sgpu_status summary_distances(DeviceIndex* d, const HostIndex& h, uint32_t list, const uint32_t* comps,
                               const float* vals, uint32_t nnz, float* out_dots, uint32_t* out_nb);
 int device_count();
 double*& call_timing();
-bool device_plan_applies(const DeviceIndex* d, const sgpu_search_params& sp);
+uint32_t device_plan_dots(DeviceIndex* d, const sgpu_search_params& sp, uint32_t nq, uint32_t cut);
 sgpu_status debug_device_plan(DeviceIndex* d, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                               uint32_t query_cut, uint32_t* order_out, uint32_t* out3);
 sgpu_status debug_plan(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                        uint32_t query_cut, uint32_t* order_out, uint32_t* out3);
 uint32_t coop_trace_dump(DeviceIndex* d, uint64_t* out, uint32_t cap);
+uint32_t debug_lane_chunk(DeviceIndex* d, uint32_t lane, uint32_t* info4, uint32_t* order_out, uint32_t cap);
 const DeviceIndex* batch_replica(const sgpu_batch* b);
 sgpu_status device_index_set_knn(DeviceIndex* d, const std::vector<uint32_t>& knn, uint32_t knn_dim);
 sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);
@@ -330,26 +331,50 @@ sgpu_status sgpu_batch_fetch_stats(sgpu_index* idx, sgpu_batch* batch, uint32_t*
 
 void sgpu_batch_destroy(sgpu_batch* batch) { batch_free(batch); }
 
-// How a shard of nq queries is cut (pure: tests/test_abi_and_host.py checks it through sgpu_debug_chunk_bounds).
-// chunk_jobs: the number of launches wanted before lanes are taken. chunk_bounds: the queries [q0, q1) of launch j of n_jobs.
+// How a shard of nq queries is cut (pure: tests/test_abi_and_host.py and tests/test_entry_chunks_cpu.py check it through
+// sgpu_debug_chunk_bounds / sgpu_debug_call_bounds).
+// chunk_jobs: the number of launches wanted before lanes are taken - never fewer than it takes to keep every chunk within
+// kChunkQueriesMax (what a lane's arena and a launch plan are sized for), up to the eight lanes of a replica.
+// chunk_bounds: the queries [q0, q1) of launch j of n_jobs (first_pm: the first chunk's share of the call in per mille,
+// 0 = equal chunks; the others share the rest equally).
+// A call of more than 8 x kChunkQueriesMax queries is served in SEGMENTS of at most that many, one after the other
+// (call_segments), each cut by the rules above: the bound on a chunk then holds whatever nq is.
 static uint32_t chunk_jobs(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max) {
-  return chunk_min && nq >= 2 * chunk_min ? std::min<uint32_t>(chunk_max, nq / chunk_min) : 1u;
+  if (!chunk_min) return 1u;
+  const uint32_t by_rule = nq >= 2 * (uint64_t)chunk_min ? std::min<uint32_t>(chunk_max, nq / chunk_min) : 1u;
+  const uint32_t by_size = (uint32_t)std::min<uint64_t>(((uint64_t)nq + kChunkQueriesMax - 1) / kChunkQueriesMax, 8u);
+  return std::max(by_rule, by_size);
 }
-static void chunk_bounds(uint32_t nq, uint32_t n_jobs, uint32_t j, uint32_t* q0, uint32_t* q1) {
-  *q0 = (uint32_t)((uint64_t)nq * j / n_jobs);
-  *q1 = (uint32_t)((uint64_t)nq * (j + 1) / n_jobs);
+static void chunk_bounds(uint32_t nq, uint32_t n_jobs, uint32_t j, uint32_t* q0, uint32_t* q1, uint32_t first_pm = 0) {
+  if (first_pm == 0 || first_pm >= 1000 || n_jobs < 2) {
+    *q0 = (uint32_t)((uint64_t)nq * j / n_jobs);
+    *q1 = (uint32_t)((uint64_t)nq * (j + 1) / n_jobs);
+    return;
+  }
+  const uint32_t first = std::min<uint32_t>(std::max<uint32_t>((uint32_t)((uint64_t)nq * first_pm / 1000), 1u), nq - (n_jobs - 1));
+  const uint32_t rest = nq - first;
+  *q0 = j == 0 ? 0u : first + (uint32_t)((uint64_t)rest * (j - 1) / (n_jobs - 1));
+  *q1 = j == 0 ? first : first + (uint32_t)((uint64_t)rest * j / (n_jobs - 1));
+}
+static uint32_t call_segments(uint32_t nq) {
+  return (uint32_t)std::max<uint64_t>(((uint64_t)nq + 8ull * kChunkQueriesMax - 1) / (8ull * kChunkQueriesMax), 1u);
 }
 
 // One shard of a batch on one replica: borrow a lane (its stream and recycled device batch), H2D of
 // the queries, one kernel pass, D2H of the results. No allocation once the lane's batch has grown to
 // the call's size; calls from different host threads take different lanes and overlap.
-// A large shard is cut into up to four chunks on as many lanes (as many as are free): the host side of
-// chunk i+1 (validation, launch plan, staging of the H2D) runs while the GPU searches chunk i, and
-// the workgroups of chunk i+1 fill the CUs that chunk i's tail leaves idle.
-// (flt: the filter of a filtered call and the replica d is, or null)
-static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
-                                const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& params,
-                                float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n, const FilterRef* flt) {
+// A large shard is cut into chunks on as many lanes (as many as are free): the host side of chunk i+1 (validation,
+// launch plan, staging of the H2D) runs while the GPU searches chunk i, and the workgroups of chunk i+1 fill the CUs
+// that chunk i's tail leaves idle. Who plans which chunk: chunk 0 goes out unplanned where the device could plan it (input
+// order, no kernel ahead of its search), every later chunk is planned HERE, on the calling thread, after the chunk before
+// it has been enqueued - the thread would only wait, and the chunk's search is then queued and ready long before the
+// previous search's workgroups start to leave (staged_launch, device_index.hip); a call that is one launch keeps the
+// device plan.
+// (flt: the filter of a filtered call and the replica d is, or null; [s0, s1): the queries of the caller's arrays this
+// segment serves - offsets, rows and error messages stay the whole shard's)
+static sgpu_status search_segment(DeviceIndex* d, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
+                                  const float* vals, uint32_t s0, uint32_t s1, uint32_t q_base, const sgpu_search_params& params,
+                                  float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n, const FilterRef* flt, bool shared) {
   static const uint32_t chunk_min = [] {
     const char* v = std::getenv("SGPU_CHUNK_MIN");
     // (600 since r03: a 1250-query call - one rank's shard of a 10 000-query batch on eight GPUs - takes 1115 us in two
@@ -371,29 +396,25 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
     const uint32_t n = v && *v ? (uint32_t)std::strtoul(v, nullptr, 10) : 0u;
     return n > 8 ? 8u : n;
   }();
-  struct InFlight {   // (counts this call on the replica for as long as it runs)
-    DeviceIndex* d;
-    bool shared;
-    explicit InFlight(DeviceIndex* d_) : d(d_), shared(call_enter(d_)) {}
-    ~InFlight() { call_exit(d); }
-  } in_flight(d);
+  // (SGPU_CHUNK_FIRST, a test hook: the first chunk's share of a call in per mille; unset or 0: equal chunks)
+  static const uint32_t chunk_first_pm = [] {
+    const char* t = std::getenv("SGPU_TEST_HOOKS");
+    const char* v = (t && *t && *t != '0') ? std::getenv("SGPU_CHUNK_FIRST") : nullptr;
+    return v && *v ? (uint32_t)std::strtoul(v, nullptr, 10) : 0u;
+  }();
+  const uint32_t nq = s1 - s0;
+  // Would chunks of this call be planned on the device? ONE predicate with staged_launch (device_plan_dots), asked with the
+  // size of a chunk of the two-way cut that answer leads to.
   // (r06: with the launch plan computed on the device - plan_kernel.hip - a chunk's host side is validation and a copy,
   // ~20 us per 1000 queries: two chunks whoever else is calling - one request thread 1.61 M queries/s against 1.59 / 1.54 M
   // with four / one, two threads 1.71 against 1.69 / 1.68; profiles/r06_entry_point_chunks.txt)
-  const uint32_t chunk_max = chunk_max_env ? chunk_max_env : ((in_flight.shared || device_plan_applies(d, params)) ? 2u : 4u);
+  const bool device_plans = device_plan_dots(d, params, std::min<uint32_t>(std::max<uint32_t>(nq / 2, 1u), kChunkQueriesMax), params.query_cut) != 0;
+  const uint32_t chunk_max = chunk_max_env ? chunk_max_env : ((shared || device_plans) ? 2u : 4u);
   Job jobs[8];
   // (r06: 1300 where the chunks are planned on the device - a 1250- or 2500-query call is then ONE launch: from two request
   // threads 864 -> 781 us and 1551 -> 1475 us per call, from one thread no difference; profiles/r06_shard_probe_chunk_min.txt)
-  const uint32_t cmin = chunk_min != 0xffffffffu ? chunk_min : (device_plan_applies(d, params) ? 1300u : 600u);
+  const uint32_t cmin = chunk_min != 0xffffffffu ? chunk_min : (device_plans ? 1300u : 600u);
   uint32_t n_jobs = chunk_jobs(nq, cmin, chunk_max);
-  std::vector<uint64_t> off;   // a chunk's offsets, rebased (sized here: nothing below allocates host memory)
-  if (n_jobs > 1) {
-    try {
-      off.resize((size_t)nq / 2 + 2);
-    } catch (const std::exception&) {
-      n_jobs = 1;
-    }
-  }
   jobs[0].lane = lane_acquire(d);
   for (uint32_t j = 1; j < n_jobs; ++j) {
     jobs[j].lane = lane_try_acquire(d);
@@ -402,26 +423,47 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
       break;
     }
   }
+  std::vector<uint64_t> off;   // a chunk's offsets, rebased (sized here: nothing below allocates host memory)
+  for (;;) {
+    uint32_t longest = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+      chunk_bounds(nq, n_jobs, j, &jobs[j].q0, &jobs[j].q1, chunk_first_pm);
+      jobs[j].q0 += s0;
+      jobs[j].q1 += s0;
+      if (jobs[j].q0 != 0) longest = std::max(longest, jobs[j].q1 - jobs[j].q0);
+    }
+    if (n_jobs == 1 && s0 == 0) break;
+    try {
+      off.resize((size_t)longest + 1);
+      break;
+    } catch (const std::exception&) {
+      if (n_jobs == 1) {
+        lane_release(d, jobs[0].lane);
+        return fail(SGPU_ENOMEM, "out of host memory cutting a query batch");
+      }
+      for (uint32_t j = 1; j < n_jobs; ++j) lane_release(d, jobs[j].lane);
+      n_jobs = 1;
+    }
+  }
   const uint32_t k = params.k;
   sgpu_status st = SGPU_OK;
   std::string msg;
   uint32_t launched = 0;
-  if (n_jobs > 1) {   // the offsets of the whole shard hold before a chunk is launched (each chunk checks its own components)
+  if (n_jobs > 1 || s0 != 0) {   // the offsets of the whole segment hold before a chunk is launched (each chunk checks its own components)
     uint32_t max_nnz = 0;
-    st = q_off[0] != 0 ? fail(SGPU_EINVAL, "q_off[0] must be 0") : validate_query_offsets(q_off, nq, q_base, &max_nnz);
+    st = q_off[0] != 0 ? fail(SGPU_EINVAL, "q_off[0] must be 0") : validate_query_offsets(q_off + s0, nq, q_base + s0, &max_nnz);
     if (st != SGPU_OK) msg = last_error();
   }
   for (uint32_t j = 0; j < n_jobs && st == SGPU_OK; ++j) {
     Job& jb = jobs[j];
-    chunk_bounds(nq, n_jobs, j, &jb.q0, &jb.q1);
     const uint64_t* qo = q_off;
-    if (n_jobs > 1 && jb.q0 != 0) {   // (a chunk that starts at query 0 uses the caller's offsets as they are)
+    if (jb.q0 != 0) {   // (a chunk that starts at query 0 uses the caller's offsets as they are)
       for (uint32_t q = jb.q0; q <= jb.q1; ++q) off[q - jb.q0] = q_off[q] - q_off[jb.q0];
       qo = off.data();
     }
     st = staged_launch(d, jb.lane, dim, qo, comps ? comps + q_off[jb.q0] : nullptr, vals ? vals + q_off[jb.q0] : nullptr,
-                       jb.q1 - jb.q0, q_base + jb.q0, params, lane_scratch(jb.lane), j + 1 < n_jobs ? 2u : (in_flight.shared ? 1u : 0u),
-                       flt);
+                       jb.q1 - jb.q0, q_base + jb.q0, params, lane_scratch(jb.lane), j + 1 < n_jobs ? 2u : (shared ? 1u : 0u),
+                       flt, j);
     if (st == SGPU_OK) ++launched;
     else msg = last_error();
   }
@@ -436,6 +478,23 @@ static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_
   }
   for (uint32_t j = 0; j < n_jobs; ++j) lane_release(d, jobs[j].lane);
   if (st != SGPU_OK) last_error() = msg;
+  return st;
+}
+
+static sgpu_status search_shard(DeviceIndex* d, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
+                                const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& params,
+                                float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n, const FilterRef* flt) {
+  struct InFlight {   // (counts this call on the replica for as long as it runs)
+    DeviceIndex* d;
+    bool shared;
+    explicit InFlight(DeviceIndex* d_) : d(d_), shared(call_enter(d_)) {}
+    ~InFlight() { call_exit(d); }
+  } in_flight(d);
+  const uint32_t n_seg = call_segments(nq);
+  sgpu_status st = SGPU_OK;
+  for (uint32_t s = 0; s < n_seg && st == SGPU_OK; ++s)
+    st = search_segment(d, dim, q_off, comps, vals, (uint32_t)((uint64_t)nq * s / n_seg), (uint32_t)((uint64_t)nq * (s + 1) / n_seg),
+                        q_base, params, out_scores, out_doc_ids, out_n, flt, in_flight.shared);
   return st;
 }
 
@@ -625,6 +684,37 @@ uint32_t sgpu_debug_chunk_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk
   if (lanes_free >= 1 && n_jobs > lanes_free) n_jobs = lanes_free;
   for (uint32_t j = 0; j < n_jobs; ++j) chunk_bounds(nq, n_jobs, j, bounds + 2 * j, bounds + 2 * j + 1);
   return n_jobs;
+}
+
+// (the same for a call of any size: its segments one after the other, each cut as above - every launch of the call in
+// order; at most `cap` launches are written, the number there are is returned)
+uint32_t sgpu_debug_call_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t lanes_free, uint32_t first_pm,
+                                uint32_t* bounds, uint32_t cap) {
+  SGPU_HOOK_OR(0u);
+  const uint32_t n_seg = call_segments(nq);
+  uint32_t n = 0;
+  for (uint32_t s = 0; s < n_seg; ++s) {
+    const uint32_t s0 = (uint32_t)((uint64_t)nq * s / n_seg), s1 = (uint32_t)((uint64_t)nq * (s + 1) / n_seg);
+    uint32_t n_jobs = chunk_jobs(s1 - s0, chunk_min, chunk_max < 1 ? 1 : (chunk_max > 8 ? 8 : chunk_max));
+    if (lanes_free >= 1 && n_jobs > lanes_free) n_jobs = lanes_free;
+    for (uint32_t j = 0; j < n_jobs; ++j, ++n) {
+      uint32_t q0, q1;
+      chunk_bounds(s1 - s0, n_jobs, j, &q0, &q1, first_pm);
+      if (n < cap) {
+        bounds[2 * n] = s0 + q0;
+        bounds[2 * n + 1] = s0 + q1;
+      }
+    }
+  }
+  return n;
+}
+
+// (the last chunk pool lane `lane` of replica 0 served: who planned it and, host-planned, the order it went down with -
+// device_index.hip debug_lane_chunk; tests/test_gpu_entry_chunks.py)
+uint32_t sgpu_debug_lane_chunk(sgpu_index* idx, uint32_t lane, uint32_t* info4, uint32_t* order_out, uint32_t cap) {
+  SGPU_HOOK_OR(0u);
+  if (!idx || !idx->dev || !info4) return 0u;
+  return debug_lane_chunk(idx->dev, lane, info4, order_out, cap);
 }
 
 // (not part of the boundary: the forward store as sgpu_index_upload packs it - document-major records - and the ref

@@ -19,6 +19,10 @@ sgpu_status fail(sgpu_status st, const char* fmt, ...) __attribute__((format(pri
 // cfs_quota_us) - a team larger than the quota is descheduled for most of every accounting period. SGPU_HOST_THREADS
 // overrides.
 int default_host_threads(int omp_max_threads);
+
+// The largest launch one chunk of an entry-point call becomes (abi.cpp: a call is cut so that no chunk exceeds it) = the
+// largest launch the device plans (device_types.hpp: kDevicePlanMaxQueries, which device_index.hip checks against this).
+constexpr uint32_t kChunkQueriesMax = 16384;
 }  // namespace sgpu
 #ifdef _OPENMP
 #include <omp.h>

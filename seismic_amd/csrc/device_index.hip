@@ -567,6 +567,8 @@ struct sgpu_batch {
                                             //   maxima come back in words 1 - 3 of the status block); 0xffffffff: host plan
   bool followed = false;                    // another chunk of the call comes after this one, or other calls are in flight
   bool plan_identity = false;               // a device-planned chunk that takes its queries in input order (staged_launch)
+  uint32_t q_base = 0;                      // the chunk's first query in the caller's batch
+  size_t order_off = 0;                     // where the launch order lies in the arena (debug_lane_chunk)
 };
 
 namespace sgpu {
@@ -918,12 +920,27 @@ sgpu_status debug_plan(const HostIndex& h, const uint64_t* q_off, const uint32_t
   return SGPU_OK;
 }
 
-// Will chunks of a call with these parameters be planned on the device (once a first chunk has seeded the cache)? abi.cpp
-// then cuts a call into fewer chunks: there is no host-side planning left to hide behind the previous chunk's kernel.
-bool device_plan_applies(const DeviceIndex* d, const sgpu_search_params& sp) {
+// May a launch of nq queries at this query_cut (`cut`: as staged_launch clamps it) be planned on the device? THE predicate:
+// staged_launch decides with it, and abi.cpp's chunk rule asks it with the size of the chunks it is about to cut. Returns
+// the block dots the LDS layout of such a launch is sized for - what earlier chunks needed (plan_dots_seen) - or 0: the host
+// plans (sizes out of range, a sorted first list, the hashed lookup of u32 indexes, SGPU_DEVICE_PLAN=0, SGPU_NO_LPT, or no
+// chunk has seeded the cache yet). The knobs are read through the per-call cache, which is refreshed here.
+static_assert((uint32_t)kDevicePlanMaxQueries == kChunkQueriesMax, "abi.cpp cuts calls by kChunkQueriesMax");
+uint32_t device_plan_dots(DeviceIndex* d, const sgpu_search_params& sp, uint32_t nq, uint32_t cut) {
+  env_refresh();
   const bool hash_family = d->comp_width == 4 && d->value_type == SGPU_VAL_F16 && d->view.dim < (1u << 24);
-  const char* v = std::getenv("SGPU_DEVICE_PLAN");
-  return sp.query_cut >= 1 && sp.query_cut <= kDevicePlanCutMax && !sp.first_sorted && !hash_family && !(v && *v == '0');
+  if (nq < kDevicePlanMinQueries || nq > kDevicePlanMaxQueries || cut < 1 || cut > kDevicePlanCutMax || sp.first_sorted ||
+      hash_family || !env_u32("SGPU_DEVICE_PLAN", 1) || hook_u32("SGPU_NO_LPT", 0))
+    return 0;
+  std::lock_guard<std::mutex> lock(d->mu);
+  const auto it = d->plan_dots_seen.find(cut);
+  return it != d->plan_dots_seen.end() ? it->second : 0u;
+}
+// (SGPU_CHUNK_PLAN=device: the later chunks of a call are planned on the device as well - see staged_launch)
+bool later_chunks_on_host() {
+  env_refresh();
+  const char* v = env_get("SGPU_CHUNK_PLAN");
+  return !(v && !std::strcmp(v, "device"));
 }
 
 // (test hook: the DEVICE's launch plan of a batch - plan_kernel.hip - in the terms of debug_plan: order, out3 = {block dots
@@ -1546,9 +1563,11 @@ static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 // (q_base: the index of the first query in the caller's batch, for error messages.)
 // (flt: the filter the chunk searches with - its view on this replica is fetched, built there on first use, once the
 // queries have passed validation; null or flt->f null: unfiltered)
+// (chunk: which launch of its call this is, 0 = the first or only one; followed: 2 = another chunk of the call comes
+// behind it, 1 = other calls are in flight on the replica)
 sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64_t* q_off, const uint32_t* comps,
                           const float* vals, uint32_t nq, uint32_t q_base, const sgpu_search_params& sp, sgpu_batch** slot,
-                          uint32_t followed, const FilterRef* flt) {
+                          uint32_t followed, const FilterRef* flt, uint32_t chunk) {
   if (!d) return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload)");
   if (sp.k == 0) return fail(SGPU_EINVAL, "k must be > 0 (KHeap::new asserts, reference src/utils.rs:23)");
   if (sp.k > 1024) return fail(SGPU_ELIMIT, "k = %u exceeds the heap limit of 1024", sp.k);
@@ -1607,6 +1626,8 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
   b->k_max = k;
   b->max_nnz = max_nnz;
   b->in_bytes = in_bytes;
+  b->q_base = q_base;
+  b->order_off = o_order;
   b->out_off = r_n;
   b->out_bytes = total - r_n;
   if (nq == 0) {
@@ -1627,18 +1648,20 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
   // one-thread call); on the host for small chunks (microseconds), for the first chunk, for a sorted first list (its
   // sort buffer must hold the chunk's largest first list: the host plan knows it exactly), for query_cut > 16 and for the
   // hashed lookup of u32 indexes (per-query seeds). SGPU_DEVICE_PLAN=0: always the host.
+  // WHO PLANS WHICH CHUNK of a call that abi.cpp cut in several: chunk 0 goes out unplanned (below) with nothing ahead of
+  // its search. A LATER chunk is planned here, on the calling thread, which would otherwise sit in its wait: the previous
+  // chunk's persistent workgroups hold every CU until its queries run out, so plan kernels on this chunk's stream cannot
+  // start before that tail (they completed 2.7 ms into a 10 000-query call) and the search behind them starts later still.
+  // Host-planned, the chunk's order goes down with its copy and its search is queued, ready, long before the previous
+  // search's first workgroup leaves; make_plan (~0.2 us per query) fits in the milliseconds that search takes. The device
+  // plan stays where it pays: a call that is ONE launch has nothing to hide a host plan behind.
+  // SGPU_CHUNK_PLAN=device: later chunks planned on the device too (the rule until this change; for A/B runs).
   b->device_plan_cut = 0xffffffffu;
   b->followed = followed != 0;
   b->plan_identity = false;
   {
-    const bool hash_family = d->comp_width == 4 && d->value_type == SGPU_VAL_F16 && d->view.dim < (1u << 24);
-    uint32_t seen = 0;
-    if (nq >= kDevicePlanMinQueries && nq <= kDevicePlanMaxQueries && cut >= 1 && cut <= kDevicePlanCutMax && !sp.first_sorted &&
-        !hash_family && env_u32("SGPU_DEVICE_PLAN", 1) && !hook_u32("SGPU_NO_LPT", 0)) {
-      std::lock_guard<std::mutex> lock(d->mu);
-      auto it = d->plan_dots_seen.find(cut);
-      if (it != d->plan_dots_seen.end()) seen = it->second;
-    }
+    uint32_t seen = device_plan_dots(d, sp, nq, cut);
+    if (seen && chunk > 0 && later_chunks_on_host()) seen = 0;
     if (seen && nq <= direct_max) seen = 0;   // (a call that small never copies its queries down: kDevicePlanMinQueries is far above, this is for the knob)
     if (!seen) {
       st = validate_queries(dim, q_off, comps, vals, nq, &max_nnz, q_base);
@@ -1662,9 +1685,13 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
     } else {
       st = make_plan(d, q_off, comps, vals, nq, cut, &b->plans.back());
       if (st != SGPU_OK) return st;
-      std::lock_guard<std::mutex> lock(d->mu);
-      uint32_t& v = d->plan_dots_seen[cut];
-      v = std::max(v, b->plans.back().dots_cap);
+      // (the host plan sizes this chunk's LDS layout exactly; it also seeds and raises what device-planned chunks are sized
+      // for - from chunks of the sizes the device plans only: a one-query latency call says nothing about a batch)
+      if (nq >= kDevicePlanMinQueries) {
+        std::lock_guard<std::mutex> lock(d->mu);
+        uint32_t& v = d->plan_dots_seen[cut];
+        v = std::max(v, b->plans.back().dots_cap);
+      }
     }
   }
   pc.lap(0);
@@ -1767,6 +1794,24 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
     return st;
   }
   return SGPU_OK;
+}
+
+// (test hook: the last chunk pool lane `lane` served - info4 = {queries, first query in its call's batch, who planned it:
+// 0 the host / 1 the device / 2 nobody (input order), query_cut} - and, host-planned, the order that went down with its
+// queries, as staged in the pinned arena. Returns 0 where the lane has served nothing. sgpu_debug_lane_chunk)
+uint32_t debug_lane_chunk(DeviceIndex* d, uint32_t lane, uint32_t* info4, uint32_t* order_out, uint32_t cap) {
+  if (!d || lane >= (uint32_t)DeviceIndex::kPool) return 0;
+  std::lock_guard<std::mutex> lk(d->pool_mu);
+  const Lane& l = d->pool[lane];
+  const sgpu_batch* b = l.scratch;
+  if (l.busy || !b || !b->staged || b->nq == 0) return 0;
+  const bool host = b->device_plan_cut == 0xffffffffu;
+  info4[0] = b->nq;
+  info4[1] = b->q_base;
+  info4[2] = host ? 0u : (b->plan_identity ? 2u : 1u);
+  info4[3] = b->order_cut;
+  if (host && order_out) std::memcpy(order_out, b->arena_host + b->order_off, (size_t)std::min<uint32_t>(cap, b->nq) * 4);
+  return 1;
 }
 
 // Waits for the lane's staged search and copies the rows out (nq x k slabs, row q padded past out_n[q]).
