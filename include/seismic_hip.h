@@ -299,12 +299,14 @@ sgpu_status sgpu_batch_run_counted(sgpu_index* idx, sgpu_batch* batch,
 sgpu_status sgpu_batch_sync(sgpu_index* idx, sgpu_launch_stats* stats);
 sgpu_status sgpu_batch_fetch(sgpu_index* idx, sgpu_batch* batch, uint32_t k,
                              float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
-/* Work counters of the batch's LAST pass, nq x 24 uint32 per query:
+/* Work counters of the batch's LAST pass (every pass starts them from zero), nq x 24 uint32, row q for query q alone:
  *   [0] blocks of the walked lists   [1] summary rows matched   [2] summary entries read
  *   [3] blocks that passed the skip test   [4] postings of those blocks
  *   [5] documents scored (as the reference would; exact after sgpu_batch_run_counted, otherwise
  *       re-encountered documents are included)   [6] sum of their component counts
  *   [7] documents the kernel scored speculatively (>= [5]; the surplus is overhead)
+ *   With a kNN graph and n_knn > 0 the neighbours the refine step scores are documents scored: they count in [5], [6]
+ *   and [7]. They are no postings of a block: [3] and [4] are those of the posting lists only.
  *   [8..19] kernel phase clocks (shader cycles / 16; zero unless the library was built with
  *           -DSGPU_PROF, `make prof`), [20] workgroup slot, [21..23] reserved
  * Counters [3..6] are exact only after sgpu_batch_run_counted (the default pass skips replay windows

@@ -453,12 +453,18 @@ class DeviceBatch:
         """B_q of SURVEY.md 8(d), summed over the batch, from the kernel's own work counters
         (val_bytes: 2 for f16 document values, 1 for fixed-u8; doc_comp_bytes: bytes per document component as
         stored, comp_width unless the component stream is compressed - 1.5 for DotVByte's 12-byte slices of eight components)."""
+        b, st = self.algorithmic_bytes_per_query(k, comp_width, val_bytes, doc_comp_bytes)
+        return int(b.sum()), st
+
+    def algorithmic_bytes_per_query(self, k, comp_width, val_bytes=2, doc_comp_bytes=None):
+        """B_q of every query of the batch (int64 [nq]; float64 where doc_comp_bytes is fractional) and the counters it
+        was computed from; algorithmic_bytes() is its sum."""
         st = self.fetch_stats().astype(np.int64)
         nnz_q = np.diff(self.q_off.astype(np.int64))
         per_elem = (comp_width if doc_comp_bytes is None else doc_comp_bytes) + val_bytes
         b = (nnz_q * (comp_width + 4) + 12 * k + 8 * st[:, 0] + 8 * st[:, 1] + 3 * st[:, 2]
              + 4 * (st[:, 4] + st[:, 3]) + 8 * st[:, 5] + st[:, 6] * per_elem)
-        return int(b.sum()), st
+        return b, st
 
     def close(self):
         if self.h:

@@ -1153,7 +1153,7 @@ SGPU_DEV void replay_chunk(RegHeap<KR>& heap, const ChunkBufs& cb, uint32_t n_it
         wc.docs += 1;
         wc.len += len;
       }
-      if (valid && lane <= last) {
+      if ((!USE_BITMAP || dots) && valid && lane <= last) {   // (counted pass: the refinement's neighbours are no postings of a block)
         wc.posts += 1;
         wc.blocks += first;
       }
@@ -1171,6 +1171,12 @@ SGPU_DEV void replay_chunk(RegHeap<KR>& heap, const ChunkBufs& cb, uint32_t n_it
     // Heap full: the window's 64 items stay in registers; every heap change re-evaluates the
     // remaining lanes against the new threshold (the reference's per-item test, 64 at a time).
     uint32_t start = 0, advance = 64;
+    if (dups && USE_BITMAP) {   // exact work counters: a later copy of a document inside this window is visited by the
+      // earlier one, as above (it cannot change the heap either way: the window is reloaded after every insertion)
+      const uint64_t nv0 = __ballot(valid && !vis);
+      for (uint32_t l = 0; l < 63; ++l)
+        if (((nv0 >> l) & 1ull) && lane > l && doc == readlane_u(doc, l)) vis = true;
+    }
     for (;;) {
       const float thr = heap.thr;
       const float cut = __fmul_rn(heap_factor, thr);
@@ -1187,8 +1193,10 @@ SGPU_DEV void replay_chunk(RegHeap<KR>& heap, const ChunkBufs& cb, uint32_t n_it
       const uint32_t f = cm ? (uint32_t)(__ffsll((long long)cm) - 1) : 63u;
       live_items += (uint32_t)__popcll(__ballot(live && lane <= f));
       if (USE_BITMAP && live && lane <= f) {   // exact work counters: the counted pass only
-        wc.posts += 1;
-        wc.blocks += first;
+        if (dots) {
+          wc.posts += 1;
+          wc.blocks += first;
+        }
         if (!vis) {
           visited_mark(bitmap, doc);
           wc.docs += 1;

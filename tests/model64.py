@@ -142,6 +142,30 @@ class Model:
             return np.zeros(0, np.int64)
         return np.unique(np.concatenate([self.list_postings(int(c)) for c in sel]))
 
+    def work_counts(self, q, query_cut, exhaustive=False):
+        """Work counters [0..2] of sgpu_batch_fetch_stats as the header defines them - blocks of the walked lists, summary
+        rows matched (rows of those lists whose component the query has), summary entries read (those rows' entries) -
+        for any search parameters; with exhaustive=True also [3..6] of a search that may skip nothing (heap_factor 0.0,
+        no negative document or query value, no graph: a summary dot is never below 0 * k-th): every block of the walked
+        lists passes, [4] = their postings, [5] = the distinct documents among them, [6] = those documents' component
+        counts. Which list wins between EQUAL query values is not the header's to say: the values must be distinct."""
+        assert len(np.unique(q.vals.astype(np.float32))) == len(q.vals), "query %d: equal values" % q.index
+        blocks = rows_n = entries = posts = 0
+        for c in self.selected_lists(q, query_cut):
+            c = int(c)
+            blocks += int(self.lbs[c + 1] - self.lbs[c])
+            rows = np.arange(self.lrs[c], self.lrs[c + 1], dtype=np.int64)
+            rows = rows[np.isin(self.row_comp[rows], q.comps)]
+            rows_n += len(rows)
+            entries += int((self.row_ptr[rows + 1] - self.row_ptr[rows]).sum())
+            posts += int(self.bps[self.lbs[c + 1]] - self.bps[self.lbs[c]])
+        out = [blocks, rows_n, entries]
+        if exhaustive:
+            assert (self.val >= 0).all() and (q.vals >= 0).all(), "query %d: negative values, blocks may be skipped" % q.index
+            pool = self.candidates(q, query_cut)
+            out += [blocks, posts, len(pool), int((self.off[pool + 1] - self.off[pool]).sum())]
+        return np.array(out, np.int64)
+
     def summary_dots(self, c, q):
         """(dot*, tolerance) per block of list c, float64."""
         b0, nb = self.lbs[c], self.lbs[c + 1] - self.lbs[c]
@@ -550,6 +574,18 @@ def edge_inputs():
         docs.append((c, v))
     cfg = dict(n_postings=40, centroid_fraction=0.15, summary_energy=0.6, max_fraction=1.5, min_cluster_size=2, doc_cut=8)
     return 2, dim, _csr(docs), cfg
+
+
+def distinct_weights(Q):
+    """The queries of Q with pairwise distinct values inside every query (rank * 2^-13 added, asserted): the inputs of
+    the work-count comparisons, where a tie between equal query values would make the walked lists a [CHOICE]."""
+    off, c, v = Q
+    v = np.asarray(v, np.float32).copy()
+    for i in range(len(off) - 1):
+        lo, hi = int(off[i]), int(off[i + 1])
+        v[lo:hi] += np.arange(hi - lo, dtype=np.float32) * np.float32(2.0 ** -13)
+        assert len(np.unique(v[lo:hi])) == hi - lo, "query %d still has equal values" % i
+    return off, c, v
 
 
 def query_at(Q, i):

@@ -184,6 +184,31 @@ def batch_search(desc, q_off, comps, vals, k, query_cut, heap_factor, first_sort
     return sc, ids, n, st.as_dict(), secs.value, used.value
 
 
+COUNT_NAMES = ("blocks_total", "rows_matched", "summary_entries", "blocks_scored", "postings_seen", "docs_scored",
+               "doc_components", "algo_bytes")
+
+
+def batch_search_counts(desc, q_off, comps, vals, k, query_cut, heap_factor, first_sorted=False,
+                        order=ORDER_LANES16, n_knn=0):
+    """batch_search's rows plus the work counts of every query on its own: (scores, ids, n, counts u64 [nq, 8]).
+    counts[:, :7] are the quantities of sgpu_batch_fetch_stats counters [0..6] (COUNT_NAMES), counts[:, 7] the query's
+    algo_bytes."""
+    q_off = np.ascontiguousarray(q_off, np.uint64)
+    comps = np.ascontiguousarray(comps, np.uint32)
+    vals = np.ascontiguousarray(vals, np.float32)
+    nq = len(q_off) - 1
+    sc = np.zeros((nq, k), np.float32)
+    ids = np.zeros((nq, k), np.uint64)
+    n = np.zeros(nq, np.uint32)
+    counts = np.zeros((nq, 8), np.uint64)
+    p = params(k, query_cut, heap_factor, first_sorted, n_knn)
+    rc = lib().orc_batch_search_counts(C.byref(desc), _p(q_off), _p(comps), _p(vals), nq, C.byref(p), order,
+                                       _p(sc), _p(ids), _p(n), _p(counts))
+    if rc:
+        raise ValueError("oracle rejected the batch (rc=%d)" % rc)
+    return sc, ids, n, counts
+
+
 def summary_distances(desc, list_id, comps, vals):
     comps = np.ascontiguousarray(comps, np.uint32)
     vals = np.ascontiguousarray(vals, np.float32)
