@@ -389,6 +389,38 @@ sgpu_status sgpu_exact_search_device_filtered(sgpu_index* idx, uint32_t replica,
                                               float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n,
                                               const sgpu_filter* filter);
 
+/* ---- scores of caller-given documents ----------------------------------------
+ * "What does THIS document score for THIS query?": reranking the candidates of another retriever, fusing candidate
+ * lists, explaining a hit, re-checking a stored result. The reference has no by-id entry point; its nearest item is
+ * QueryEvaluator::compute_distance at its call site src/posting_list.rs:210-211, the score its search computes for
+ * a document of a posting list.
+ * Query q = [q_off[q], q_off[q+1]) as in sgpu_batch_search; its candidates are
+ * cand_ids[cand_off[q] .. cand_off[q+1]) (native document ids, any order, repeats allowed, possibly none).
+ * out_scores[i] is the score of cand_ids[i] for its query: one float per candidate, cand_off[nq] in all.
+ * A score is, bit for bit, the score sgpu_search / sgpu_batch_search return for that document and query: the full query's
+ * dot product over the document's stored values in the canonical order - 16 accumulators, element e of the document to
+ * accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
+ * add, never contracted; components the query does not carry, and query components of weight +-0, contribute nothing. A
+ * document without components scores +0.0, as does every document for an empty query. Scores that are not finite (inf
+ * query values) need not match. Every value type, component width and forward layout.
+ * Checks, in this order: null arguments (SGPU_EINVAL; cand_ids and out_scores too, also when there is no candidate), the
+ * queries (SGPU_EINVAL), cand_off[0] != 0 or cand_off decreasing (SGPU_EINVAL), a document id >= n_docs (SGPU_EINVAL; the
+ * message names the first one and its query), a query of more than 8192 components (SGPU_ELIMIT), index not uploaded or
+ * replica out of range (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays usable). nq == 0 or no candidate at
+ * all is SGPU_OK.
+ * Safe to call while other threads search the same replica: the call has a stream of its own; score calls on one replica
+ * take turns. Its scratch on the device (the staged queries, ids and scores) is kept per replica and recycled, freed by
+ * sgpu_index_destroy or a new upload, and not counted by sgpu_index_device_bytes; no index array is added. A call of more
+ * candidates than a launch's budget (2^20; environment SGPU_SCORE_CHUNK overrides) runs as several launches. */
+sgpu_status sgpu_score_documents(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, float* out_scores);
+/* The same on the host cores (needs no upload), bit-identical; the same checks without the device ones.
+ * num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_score_documents_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads, float* out_scores);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

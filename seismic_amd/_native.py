@@ -86,6 +86,8 @@ def lib():
         L.sgpu_exact_search_filtered.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.sgpu_exact_search_device_filtered.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp,
                                                         vp]
+        L.sgpu_score_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]
+        L.sgpu_score_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -351,6 +353,31 @@ class NativeIndex:
             check(lib().sgpu_exact_search_device_filtered(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, k,
                                                           _p(sc), _p(ids), _p(n), _filter_handle(filter)))
         return sc, ids, n[:nq]
+
+    # ---- scores of caller-given documents ----
+    def score_documents(self, q_off, comps, vals, cand_off, cand_ids, replica=0):
+        """sgpu_score_documents: query q's candidates are cand_ids[cand_off[q] : cand_off[q + 1]] (native document ids, any
+        order, repeats allowed); returns one f32 per candidate - the score sgpu_search returns for that document, bit for
+        bit. Runs on the device of `replica`."""
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        out = np.zeros(max(len(cand_ids), 1), np.float32)
+        ids = cand_ids if len(cand_ids) else np.zeros(1, np.uint64)
+        check(lib().sgpu_score_documents(self.h, int(replica), _p(q_off), _p(comps), _p(vals), len(q_off) - 1,
+                                         _p(cand_off), _p(ids), _p(out)))
+        return out[: len(cand_ids)]
+
+    def score_documents_host(self, q_off, comps, vals, cand_off, cand_ids, num_threads=0):
+        """sgpu_score_documents_host: the same scores on the host cores (needs no upload), bit-identical."""
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        out = np.zeros(max(len(cand_ids), 1), np.float32)
+        ids = cand_ids if len(cand_ids) else np.zeros(1, np.uint64)
+        check(lib().sgpu_score_documents_host(self.h, _p(q_off), _p(comps), _p(vals), len(q_off) - 1, _p(cand_off),
+                                              _p(ids), int(num_threads), _p(out)))
+        return out[: len(cand_ids)]
 
 
 def _filter_handle(f):

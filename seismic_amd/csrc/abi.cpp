@@ -58,6 +58,11 @@ sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);
 sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
                                 uint32_t* out_n, const sgpu_filter* filter);
+// score_documents.hip
+sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                   const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
+                                   float* out_scores);
+bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
 const sgpu_index* filter_index(const sgpu_filter* f);
@@ -160,6 +165,8 @@ struct GenerationBump {
 static void drop_replicas(sgpu_index* idx) {
   for (ExactFile* f : idx->exact) exact_file_free(f);
   idx->exact.clear();
+  for (ScoreState* s : idx->score) score_state_free(s);
+  idx->score.clear();
   for (DeviceIndex* d : idx->replicas) device_index_free(d);
   idx->replicas.clear();
   idx->dev = nullptr;
@@ -830,6 +837,29 @@ sgpu_status sgpu_exact_search_device_filtered(sgpu_index* idx, uint32_t replica,
   const sgpu_status st = foreign_filter(idx, filter);
   if (st != SGPU_OK) return st;
   return exact_search_device(idx, replica, q_off, comps, vals, nq, k, out_scores, out_doc_ids, out_n, filter);
+}
+
+sgpu_status sgpu_score_documents(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                 const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
+                                 float* out_scores) {
+  return score_documents_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, out_scores);
+}
+
+sgpu_status sgpu_score_documents_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                      uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads,
+                                      float* out_scores) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  return score_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, num_threads, out_scores);
+}
+
+// (not part of the boundary: what the last sgpu_score_documents call on `replica` measured - out8 = {device ms of its
+// kernels, launches, 1 = dense table / 0 = hash table, grid, workgroup size, LDS bytes, 0, 0}; SGPU_EINVAL before the
+// replica's first score call. tools/score_probe.py)
+sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");
+  if (!score_debug_stats(idx, replica, out8)) return fail(SGPU_EINVAL, "no score call has run on replica %u", replica);
+  return SGPU_OK;
 }
 
 // (not part of the boundary: device and wall milliseconds of the build of the filter's view on `replica`; SGPU_EINVAL

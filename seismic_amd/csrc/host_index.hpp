@@ -11,6 +11,7 @@ namespace sgpu {
 
 struct DeviceIndex;  // search.hip
 struct ExactFile;    // exact_device.hip
+struct ScoreState;   // score_documents.hip
 
 struct HostIndex {
   uint32_t comp_width = 2;
@@ -93,6 +94,14 @@ sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const 
                               float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* allow = nullptr);
 // exact_device.hip
 void exact_file_free(ExactFile* f);
+// score_host.cpp: scores of caller-given documents (sgpu_score_documents_host) and the argument checks both calls run
+constexpr uint32_t kScoreMaxQueryNnz = 8192;   // components of a query (the device's hash table: 2^14 slots, half full)
+sgpu_status score_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                             const uint64_t* cand_off, const uint64_t* cand_ids, const float* out_scores, uint32_t* max_nnz);
+sgpu_status score_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                 const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads, float* out_scores);
+// score_documents.hip
+void score_state_free(ScoreState* s);
 
 // filter.hip: which filter a launch searches with (f null: none) and on which replica of the index
 struct FilterRef {
@@ -110,6 +119,8 @@ struct sgpu_index {
   std::atomic<uint32_t> next_replica{0};      // calls too small to shard go to the replicas in turn
   std::vector<sgpu::ExactFile*> exact;        // per replica: the exact file (null until its first exact call)
   std::mutex exact_mu;                        // its lazy build
+  std::vector<sgpu::ScoreState*> score;       // per replica: stream and scratch of sgpu_score_documents (null until its first call)
+  std::mutex score_mu;                        // their creation
   // bumped by every call that replaces device state a filter's views derive from (upload, upload_many, set_knn,
   // build_knn): a view built under an older generation is rebuilt on its next use, never dereferenced (filter.hip)
   std::atomic<uint64_t> generation{0};

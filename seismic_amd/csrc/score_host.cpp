@@ -1,0 +1,85 @@
+// score_host.cpp — sgpu_score_documents_host, and the argument checks it shares with the device call.
+//
+// The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
+// accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
+// add (this file is compiled with -ffp-contract=off). A query is scattered into a dense f32 table over the vocabulary
+// (one per thread); components it does not carry read 0.0 and are added as +-0.0, which never changes an accumulator
+// that started at +0.0. Fixed-u8 codes: the power of two val_scale is folded into the weight, as on the device.
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "host_index.hpp"
+
+namespace sgpu {
+
+// Checks 1 - 5 of sgpu_score_documents, in the header's order.
+sgpu_status score_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                             const uint64_t* cand_off, const uint64_t* cand_ids, const float* out_scores, uint32_t* max_nnz) {
+  if (!q_off || !cand_off || !cand_ids || !out_scores) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = validate_queries(h.dim, q_off, comps, vals, nq, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (cand_off[0] != 0) return fail(SGPU_EINVAL, "cand_off[0] must be 0");
+  for (uint32_t q = 0; q < nq; ++q)
+    if (cand_off[q + 1] < cand_off[q]) return fail(SGPU_EINVAL, "cand_off not monotone");
+  for (uint32_t q = 0; q < nq; ++q)
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i)
+      if (cand_ids[i] >= h.n_docs)
+        return fail(SGPU_EINVAL, "query %u: document id %llu >= n_docs (%llu)", q, (unsigned long long)cand_ids[i],
+                    (unsigned long long)h.n_docs);
+  if (*max_nnz > kScoreMaxQueryNnz)
+    return fail(SGPU_ELIMIT, "a query has %u components (scoring documents: limit %u)", *max_nnz, kScoreMaxQueryNnz);
+  return SGPU_OK;
+}
+
+static inline float score_one(const HostIndex& h, uint64_t doc, const float* dense) {
+  const uint64_t s = h.fwd_offsets[doc], e = h.fwd_offsets[doc + 1];
+  float t[16];
+  for (int j = 0; j < 16; ++j) t[j] = 0.0f;
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+  for (uint64_t i = s; i < e; ++i) {
+    const float v = f16 ? f16_to_f32(h.fwd_vals[i]) : (float)h.fwd_codes[i];
+    const int lane = (int)(((i - s) >> 3) & 15);
+    const float p = dense[h.comp(i)] * v;
+    t[lane] = t[lane] + p;
+  }
+  for (int st = 8; st >= 1; st >>= 1) {
+    float u[16];
+    for (int j = 0; j < 16; ++j) u[j] = t[j] + t[j ^ st];
+    for (int j = 0; j < 16; ++j) t[j] = u[j];
+  }
+  return t[0];
+}
+
+sgpu_status score_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                 const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads, float* out_scores) {
+  uint32_t max_nnz = 0;
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out_scores, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0 || cand_off[nq] == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  std::vector<std::vector<float>> tables;
+  try {
+    tables.assign((size_t)team, std::vector<float>());
+    for (auto& t : tables) t.assign(h.dim, 0.0f);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+    if (cand_off[q + 1] == cand_off[q]) continue;
+#ifdef _OPENMP
+    float* dense = tables[(size_t)omp_get_thread_num()].data();
+#else
+    float* dense = tables[0].data();
+#endif
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) out_scores[i] = score_one(h, cand_ids[i], dense);
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+  }
+  return SGPU_OK;
+}
+
+}  // namespace sgpu

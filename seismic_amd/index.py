@@ -311,8 +311,58 @@ class SeismicDatasetLV(_DatasetBase):
     _CW = 4
 
 
+
 # ---------------------------------------------------------------------------
-class _IndexBase:
+class _ScoreMixin:
+    """score / batch_score / batch_rerank of the index classes: the scores of caller-given documents
+    (sgpu_score_documents; no reference counterpart - the reference computes such a score only inside its search,
+    QueryEvaluator::compute_distance at src/posting_list.rs:210-211). A score is what search returns for the document,
+    bit for bit. The classes supply _score_queries (queries -> CSR, unknown tokens dropped as in search),
+    _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id)."""
+
+    def _batch_score_native(self, query_components, query_values, doc_ids_per_query, device):
+        off, comps, vals = self._score_queries(query_components, query_values)
+        rows = [self._score_rows(d) for d in doc_ids_per_query]
+        if len(rows) != len(off) - 1:
+            raise ValueError("%d queries but %d document id lists" % (len(off) - 1, len(rows)))
+        cand_off = np.zeros(len(rows) + 1, np.uint64)
+        if rows:
+            cand_off[1:] = np.cumsum([len(r) for r in rows])
+        cand = np.concatenate(rows).astype(np.uint64) if rows else np.zeros(0, np.uint64)
+        if device is False:
+            sc = self._ix.score_documents_host(off, comps, vals, cand_off, cand)
+        else:
+            if device is not None and device is not True and int(device) != int(self._device):
+                raise ValueError("the index is on device %d, not %d" % (self._device, int(device)))
+            self._ensure_device()
+            sc = self._ix.score_documents(off, comps, vals, cand_off, cand)
+        bounds = cand_off.astype(np.int64)
+        return [sc[bounds[i]:bounds[i + 1]] for i in range(len(rows))], rows
+
+    def batch_score(self, query_components, query_values, doc_ids_per_query, device=None):
+        """Per query, the scores (float32 array) of its documents doc_ids_per_query[q], in the order given (any order,
+        repeats allowed, possibly none). device None: the GPU the index is on; False: the host cores, bit-identical."""
+        return self._batch_score_native(query_components, query_values, doc_ids_per_query, device)[0]
+
+    def score(self, query_components, query_values, doc_ids, device=None):
+        """The scores (float32 array) of the documents `doc_ids` for one query."""
+        return self.batch_score([query_components], [query_values], [doc_ids], device)[0]
+
+    def batch_rerank(self, query_components, query_values, doc_ids_per_query, k, device=None):
+        """Per query the k best of its candidates -> [[(score, doc_id)]]: score descending, ties by native document id
+        ascending, a candidate given more than once counted once."""
+        scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
+        out = []
+        for sc, r in zip(scores, rows):
+            ids, first = np.unique(np.asarray(r, np.int64), return_index=True)   # (ascending native ids)
+            s = sc[first]
+            order = np.argsort(-s.astype(np.float64), kind="stable")[: int(k)]   # (stable: ties keep ascending ids)
+            out.append([(float(s[i]), self._score_name(int(ids[i]))) for i in order])
+        return out
+
+
+# ---------------------------------------------------------------------------
+class _IndexBase(_ScoreMixin):
     _CW = 2
 
     def __init__(self, native, token_map, doc_ids, contents=None, device=0, upload=True):
@@ -511,6 +561,24 @@ class _IndexBase:
             rows.append(i)
         return SeismicFilter(self, self._ix.make_filter(np.asarray(rows, np.int64)))
 
+    # ---- scores of given documents (_ScoreMixin) ----------------------
+    def _score_queries(self, query_components, query_values):
+        return _resolve_batch(query_components, query_values, self._tm, lambda t: np.asarray(t).astype(str))
+
+    def _score_rows(self, doc_ids):
+        if isinstance(doc_ids, (str, bytes)):
+            raise TypeError("document ids come as an iterable, not a single id")
+        pos, rows = self._positions(), []
+        for d in doc_ids:
+            i = pos.get(str(d))
+            if i is None:
+                raise KeyError(d)
+            rows.append(i)
+        return np.asarray(rows, np.int64)
+
+    def _score_name(self, row):
+        return self._doc_ids[row]
+
     # ---- search -------------------------------------------------------
     def _remap(self, query_id, sc, ids, n):
         n, q, names = int(n), str(query_id), self._doc_ids
@@ -594,7 +662,7 @@ class SeismicIndexDotVByte(_IndexBase):
 
 
 # ---------------------------------------------------------------------------
-class _RawBase:
+class _RawBase(_ScoreMixin):
     """Integer-keyed index over the inner binary format (reference src/pylib/mod.rs:663-1151)."""
     _CW = 2
 
@@ -654,6 +722,29 @@ class _RawBase:
         filter= to search and batch_search."""
         return SeismicFilter(self, self._ix.make_filter(np.asarray(list(doc_ids) if not isinstance(doc_ids, np.ndarray)
                                                                    else doc_ids)))
+
+    def _score_queries(self, query_components, query_values):
+        off = np.zeros(len(query_components) + 1, np.uint64)
+        cs, vs = [], []
+        for i, (qc, qv) in enumerate(zip(query_components, query_values)):
+            c = np.asarray(qc).astype(np.uint32).ravel()
+            v = np.asarray(qv, np.float32).ravel()
+            order = np.argsort(c, kind="stable")
+            cs.append(c[order])
+            vs.append(v[order])
+            off[i + 1] = off[i] + len(c)
+        return (off, np.concatenate(cs) if cs else np.zeros(0, np.uint32),
+                np.concatenate(vs) if vs else np.zeros(0, np.float32))
+
+    def _score_rows(self, doc_ids):
+        rows = np.asarray(list(doc_ids) if not isinstance(doc_ids, np.ndarray) else doc_ids).astype(np.int64).ravel()
+        bad = rows[(rows < 0) | (rows >= self.len)]
+        if len(bad):
+            raise KeyError(int(bad[0]))
+        return rows
+
+    def _score_name(self, row):
+        return row
 
     def search(self, query_components, query_values, k, query_cut, heap_factor, n_knn, sorted, filter=None):
         """-> [(score, doc_id)] (reference src/pylib/mod.rs:1033-1076). filter: a SeismicFilter of this index or an
