@@ -421,6 +421,37 @@ sgpu_status sgpu_score_documents_host(const sgpu_index* idx,
     const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
     const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads, float* out_scores);
 
+/* ---- rerank: the k best of each query's candidates ----------------------------
+ * The second stage in one call: the candidates are scored as by sgpu_score_documents and the selection runs on the
+ * device too, so only nq x k rows come back. Queries and candidates are given exactly as for sgpu_score_documents (any
+ * order, repeats allowed, possibly none).
+ * Row q of the nq x k row-major outputs holds the DISTINCT document ids among query q's candidates, ordered by score
+ * descending, ties by document id ascending, cut to the first k; out_n[q] = min(k, distinct candidates of q). Slots past
+ * out_n[q] are written as zero, as sgpu_batch_search does. A query without candidates gets out_n = 0 and a zeroed row.
+ * Each returned score is, bit for bit, what sgpu_score_documents and sgpu_search return for that pair. A score is never
+ * -0.0: every accumulator starts at +0.0 and is only added to, and x + y is -0.0 only if both are; so numeric order and
+ * the order of the monotone integer image of the f32 bits agree on finite scores, and the device selects on that image.
+ * The host twin places NaN scores after every number, by id ascending; device rows that contain a score that is not
+ * finite need not match it (sgpu_score_documents makes the same reservation).
+ * Checks, in this order: null arguments (SGPU_EINVAL; cand_ids, out_scores, out_doc_ids and out_n too, also when there is
+ * nothing to do), everything sgpu_score_documents checks in its order, k == 0 (SGPU_EINVAL), k > 1024 (SGPU_ELIMIT), index
+ * not uploaded or replica out of range (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays usable). nq == 0 is
+ * SGPU_OK.
+ * The call shares the score calls' per-replica stream and recycled scratch and takes turns with them; it is safe beside
+ * searches, filtered and exact calls. It adds no index array; its scratch is freed by sgpu_index_destroy or a new upload.
+ * A call of more candidates than a launch's budget (2^20; SGPU_SCORE_CHUNK overrides) runs as several launches, also
+ * where the cut falls inside one query's candidates; the rows do not depend on where the cuts fall. */
+sgpu_status sgpu_rerank_documents(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
+    float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
+/* The same on the host cores (needs no upload): the same rows, bit for bit, wherever every score is finite; the same
+ * checks without the device ones. num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_rerank_documents_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, uint32_t num_threads,
+    float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

@@ -36,8 +36,10 @@ sgpu_status sgpu_debug_device_plan(sgpu_index* idx, const uint64_t* q_off, const
 void sgpu_debug_call_timing(double* buf8);
 /* timeline of the last cooperative launch (trace builds) */
 uint32_t sgpu_debug_coop_trace(sgpu_index* idx, uint64_t* out, uint32_t cap);
-/* what the last sgpu_score_documents call on `replica` measured: out8 = {device ms of its kernels (HIP events), launches,
- * 1 = dense weight table / 0 = hash table, grid, workgroup size, LDS bytes, 0, 0}; SGPU_EINVAL before the first call */
+/* what the last sgpu_score_documents / sgpu_rerank_documents call on `replica` measured: out8 = {device ms of its score
+ * kernels (HIP events), launches, 1 = dense weight table / 0 = hash table, grid, workgroup size, LDS bytes, device ms of
+ * the selection kernels (0 for a score call), merge rounds the selection ran after its chunk round, summed over the
+ * call's launches}; SGPU_EINVAL before the first call */
 sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* out8);
 
 #ifdef __cplusplus

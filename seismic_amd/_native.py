@@ -88,6 +88,8 @@ def lib():
                                                         vp]
         L.sgpu_score_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]
         L.sgpu_score_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+        L.sgpu_rerank_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp]
+        L.sgpu_rerank_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -378,6 +380,38 @@ class NativeIndex:
         check(lib().sgpu_score_documents_host(self.h, _p(q_off), _p(comps), _p(vals), len(q_off) - 1, _p(cand_off),
                                               _p(ids), int(num_threads), _p(out)))
         return out[: len(cand_ids)]
+
+    # ---- the k best of each query's candidates ----
+    @staticmethod
+    def _rerank_buffers(q_off, comps, vals, cand_off, cand_ids, k):
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        nq, k = len(q_off) - 1, int(k)
+        if not 0 <= k < 2 ** 32:
+            raise ValueError("k = %d" % k)
+        rows = (max(nq, 1), k if 1 <= k <= 1024 else 1)   # (a k the library refuses: nothing is written)
+        sc = np.zeros(rows, np.float32)
+        ids = np.zeros(rows, np.uint64)
+        n = np.zeros(max(nq, 1), np.uint32)
+        cand = cand_ids if len(cand_ids) else np.zeros(1, np.uint64)
+        return q_off, comps, vals, cand_off, cand, nq, k, sc, ids, n
+
+    def rerank_documents(self, q_off, comps, vals, cand_off, cand_ids, k, replica=0):
+        """sgpu_rerank_documents: per query the k best DISTINCT documents among its candidates (given as for
+        score_documents), score descending, ties by id ascending, scored and selected on the device of `replica`.
+        Returns (scores f32 [nq, k], ids u64 [nq, k], n u32 [nq]); slots past n[q] are zero."""
+        q_off, comps, vals, cand_off, cand, nq, k, sc, ids, n = self._rerank_buffers(q_off, comps, vals, cand_off, cand_ids, k)
+        check(lib().sgpu_rerank_documents(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand),
+                                          k, _p(sc), _p(ids), _p(n)))
+        return sc[:nq], ids[:nq], n[:nq]
+
+    def rerank_documents_host(self, q_off, comps, vals, cand_off, cand_ids, k, num_threads=0):
+        """sgpu_rerank_documents_host: the same rows on the host cores (needs no upload)."""
+        q_off, comps, vals, cand_off, cand, nq, k, sc, ids, n = self._rerank_buffers(q_off, comps, vals, cand_off, cand_ids, k)
+        check(lib().sgpu_rerank_documents_host(self.h, _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), k,
+                                               int(num_threads), _p(sc), _p(ids), _p(n)))
+        return sc[:nq], ids[:nq], n[:nq]
 
 
 def _filter_handle(f):

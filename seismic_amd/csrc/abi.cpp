@@ -62,6 +62,9 @@ sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_
 sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                    const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
                                    float* out_scores);
+sgpu_status rerank_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                    const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
+                                    float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
 bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
@@ -852,9 +855,24 @@ sgpu_status sgpu_score_documents_host(const sgpu_index* idx, const uint64_t* q_o
   return score_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, num_threads, out_scores);
 }
 
-// (not part of the boundary: what the last sgpu_score_documents call on `replica` measured - out8 = {device ms of its
-// kernels, launches, 1 = dense table / 0 = hash table, grid, workgroup size, LDS bytes, 0, 0}; SGPU_EINVAL before the
-// replica's first score call. tools/score_probe.py)
+sgpu_status sgpu_rerank_documents(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                  const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
+                                  float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n) {
+  return rerank_documents_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, k, out_scores, out_doc_ids, out_n);
+}
+
+sgpu_status sgpu_rerank_documents_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                       uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
+                                       uint32_t num_threads, float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  return rerank_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, k, num_threads, out_scores, out_doc_ids,
+                               out_n);
+}
+
+// (not part of the boundary: what the last sgpu_score_documents / sgpu_rerank_documents call on `replica` measured - out8 =
+// {device ms of its score kernels, launches, 1 = dense table / 0 = hash table, grid, workgroup size, LDS bytes, device ms of
+// the selection kernels, merge rounds}; SGPU_EINVAL before the replica's first score call. tools/score_probe.py,
+// tools/rerank_probe.py)
 sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* out8) {
   SGPU_HOOK_OR(SGPU_EINVAL);
   if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");

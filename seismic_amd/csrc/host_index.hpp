@@ -100,6 +100,14 @@ sgpu_status score_check_args(const HostIndex& h, const uint64_t* q_off, const ui
                              const uint64_t* cand_off, const uint64_t* cand_ids, const float* out_scores, uint32_t* max_nnz);
 sgpu_status score_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                  const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads, float* out_scores);
+// the k best distinct candidates of each query (sgpu_rerank_documents_host) and checks 1 - 4 both rerank calls run
+constexpr uint32_t kRerankMaxK = 1024;
+sgpu_status rerank_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                              const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, const float* out_scores,
+                              const uint64_t* out_doc_ids, const uint32_t* out_n, uint32_t* max_nnz);
+sgpu_status rerank_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                  const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, uint32_t num_threads,
+                                  float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
 // score_documents.hip
 void score_state_free(ScoreState* s);
 

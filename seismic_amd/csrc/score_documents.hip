@@ -16,6 +16,33 @@
 //   raw      [npad components (u16 / u32)][npad values (binary16 / u8 codes)], npad = len rounded up to 8
 //   sliced   (DotVByte) [ns x 16 B: 96 bits of first component + gaps | codes 0-3][ns x 4 B: codes 4-7], ns = npad / 8;
 //            bit 15 of the ref's length field: the document keeps the raw (u16, u8) form instead
+//
+// sgpu_rerank_documents adds the SELECTION on the device: per query the k best DISTINCT candidates, score descending, id
+// ascending. score_documents_kernel is used as it is and leaves a launch's scores in the device scratch; what follows it
+// on the same stream is rerank_select_kernel, once per round.
+//   key     ordered(score bits) << 32 | ~id, a u64: ordered() is the monotone integer image of an f32 (flip all bits of
+//           a negative, the sign bit of the others), so a larger key is a better candidate - higher score, then lower
+//           id. A score is never -0.0 (accumulators start at +0.0 and are only added to), so the image's order is the
+//           numeric order on finite scores. Equal ids carry equal scores, hence equal keys: after a descending sort a
+//           duplicate is a key equal to its predecessor. Key 0 (the image of the NaN 0xffffffff with id 2^32 - 1, which
+//           no finite score has) is the padding.
+//   task    a TEAM of threads takes at most `cap` keys of ONE query - a chunk of the launch's candidates (keys made from
+//           score and id) or the survivors of earlier tasks (k-key slots) -, sorts them in LDS (bitonic, descending,
+//           padded to cap with 0), drops the duplicates and the padding, compacts (a prefix sum over the team) and
+//           writes the first k: to the query's result row if the task is the query's last, else to a slot, zero-padded.
+//   rounds  round 0 holds the chunk tasks of every query part of the launch, round r > 0 merges each part's slots of
+//           round r - 1 in groups of floor(C / k) >= 2 until one task is left; rounds are separate launches on the
+//           call's stream, which is all the ordering there is (no loop waits on another workgroup). Correct because the
+//           distinct top-k of a union is the distinct top-k of the union of the parts' distinct top-k.
+//   carry   a query cut by a launch boundary ends its part in one of two carry slots; its next part's first merge task
+//           takes that slot as one more source. Only one query can be open at a boundary; the slots alternate, because
+//           a launch's last part may write its carry in round 0 while its first part reads the other in a later round.
+//   sizes   C = 2048 keys: the smallest C with floor(C / k) >= 2 at k = 1024; 16 KiB of LDS per 256-thread workgroup,
+//           so the 8 workgroups that fill a CU's 2048 threads hold 128 of its 160 KiB. A larger C buys fewer merge rounds
+//           with more bitonic steps (log2(C) (log2(C) + 1) / 2 barriers each) and fewer workgroups per CU. A task of few
+//           keys goes to a smaller tier instead of being padded to C: 128 keys per wave64 (four tasks per workgroup, 28
+//           steps of one compare-exchange per lane: the 10 000 x 100 shape) or 512 keys per wave64. Every workgroup has
+//           256 threads; the barriers of the tiers' fixed step counts are uniform over it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -247,6 +274,138 @@ ScoreKernel score_kernel(uint32_t cw, uint32_t vt, bool dense) {
   return dense ? score_documents_kernel<4, SVT_F16, true> : score_documents_kernel<4, SVT_F16, false>;
 }
 
+
+// ---- selection (sgpu_rerank_documents) ----
+constexpr uint32_t kRerankChunk = 2048;   // C: keys a workgroup-wide team sorts (test hook SGPU_RERANK_CHUNK lowers it)
+constexpr uint32_t kSelBlock = 256;
+constexpr uint32_t kSelNone = 0xffffffffu;
+struct SelTier {
+  uint32_t cap, team;   // keys per task (a power of two), threads per task (a multiple of 64 dividing kSelBlock)
+};
+constexpr SelTier kSelTiers[3] = {{128, 64}, {512, 64}, {kRerankChunk, 256}};
+enum { SEL_RAW = 0, SEL_KEYS = 1 };             // a task's source
+enum { SEL_TO_SLOT = 0, SEL_TO_ROW = 1, SEL_TO_CARRY = 2 };   // ... and its destination
+
+struct SelTask {   // 32 bytes
+  uint32_t kind;       // SEL_RAW: candidates [src, src + n) of the launch; SEL_KEYS: slots [src, src + n)
+  uint32_t src, n;
+  uint32_t extra;      // SEL_KEYS: a carry slot (0 / 1) that is one more source, or kSelNone
+  uint32_t dst_kind;
+  uint32_t dst;        // slot, query (its row) or carry slot
+  uint32_t pad0, pad1;
+};
+
+struct SelArgs {
+  const SelTask* tasks;
+  const float* scores;      // the launch's scores and candidate ids (SEL_RAW)
+  const uint32_t* cand;
+  uint64_t* slots;          // k keys each
+  uint64_t* carry;          // 2 slots
+  float* row_scores;        // the call's rows [nq x k], zeroed before the first launch
+  uint64_t* row_ids;
+  uint32_t* row_n;
+  uint32_t n_tasks, cap, team, k;
+};
+
+__device__ __forceinline__ uint64_t sel_key(float score, uint32_t id) {
+  const uint32_t b = __float_as_uint(score);
+  const uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ((uint64_t)o << 32) | (uint64_t)(~id);
+}
+__device__ __forceinline__ float sel_key_score(uint64_t key) {
+  const uint32_t o = (uint32_t)(key >> 32);
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+__global__ __launch_bounds__(kSelBlock) void rerank_select_kernel(SelArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ uint32_t wave_total[kSelBlock / 64];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t cap = a.cap, team = a.team, k = a.k;
+  const uint32_t teams = kSelBlock / team, tm = tid / team, lt = tid % team;
+  const uint32_t waves = team / 64u, w = tid >> 6, lane = tid & 63u;
+  uint64_t* key = (uint64_t*)smem + (size_t)tm * cap;
+  const uint32_t per = cap >= team ? cap / team : 1u;   // consecutive sorted keys a thread looks at
+  // (every bound below is workgroup-uniform: a team without a task runs the same barriers over padding)
+  for (uint32_t base = blockIdx.x * teams; base < a.n_tasks; base += gridDim.x * teams) {
+    const bool live = base + tm < a.n_tasks;
+    SelTask t{};
+    if (live) t = a.tasks[base + tm];
+    const uint32_t n_src = t.kind == SEL_RAW ? t.n : t.n * k;            // keys of the contiguous source
+    const uint32_t n_all = n_src + (t.kind == SEL_KEYS && t.extra != kSelNone ? k : 0u);   // (<= cap: the host's cut)
+    for (uint32_t i = lt; i < cap; i += team) {
+      uint64_t v = 0;
+      if (i < n_src) {
+        v = t.kind == SEL_RAW ? sel_key(a.scores[t.src + i], a.cand[t.src + i]) : a.slots[(size_t)t.src * k + i];
+      } else if (i < n_all) {
+        v = a.carry[(size_t)t.extra * k + (i - n_src)];
+      }
+      key[i] = v;
+    }
+    __syncthreads();
+    for (uint32_t size = 2; size <= cap; size <<= 1)
+      for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+        for (uint32_t p = lt; p < (cap >> 1); p += team) {
+          const uint32_t i = 2u * p - (p & (stride - 1u)), j = i + stride;
+          const uint64_t x = key[i], y = key[j];
+          const bool desc = (i & size) == 0u;
+          if ((x < y) == desc && x != y) {
+            key[i] = y;
+            key[j] = x;
+          }
+        }
+        __syncthreads();
+      }
+    // distinct keys that are no padding, counted per thread over its run of the sorted keys ...
+    uint32_t cnt = 0;
+    const uint32_t e0 = lt * per;
+    if (e0 < cap)
+      for (uint32_t e = e0; e < e0 + per; ++e) {
+        const uint64_t v = key[e];
+        cnt += (v != 0 && (e == 0 || v != key[e - 1])) ? 1u : 0u;
+      }
+    // ... and their exclusive prefix sum over the team: within a wave by shuffles, across its waves through LDS
+    uint32_t incl = cnt;
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+      const uint32_t u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (lane == 63u) wave_total[w] = incl;
+    __syncthreads();
+    uint32_t before = incl - cnt, total = 0;
+    for (uint32_t x = 0; x < waves; ++x) {
+      const uint32_t wt = wave_total[tm * waves + x];
+      if (tm * waves + x < w) before += wt;
+      total += wt;
+    }
+    const uint32_t kept = min(total, k);
+    if (live) {
+      uint64_t* dst_keys = t.dst_kind == SEL_TO_SLOT ? a.slots + (size_t)t.dst * k : a.carry + (size_t)t.dst * k;
+      const bool row = t.dst_kind == SEL_TO_ROW;
+      if (e0 < cap) {
+        uint32_t pos = before;
+        for (uint32_t e = e0; e < e0 + per && pos < k; ++e) {
+          const uint64_t v = key[e];
+          if (v != 0 && (e == 0 || v != key[e - 1])) {
+            if (row) {
+              a.row_scores[(size_t)t.dst * k + pos] = sel_key_score(v);
+              a.row_ids[(size_t)t.dst * k + pos] = (uint64_t)(~(uint32_t)v);
+            } else {
+              dst_keys[pos] = v;
+            }
+            ++pos;
+          }
+        }
+      }
+      if (row) {
+        if (lt == 0) a.row_n[t.dst] = kept;   // (the row's other slots are zero since the call's start)
+      } else {
+        for (uint32_t i = kept + lt; i < k; i += team) dst_keys[i] = 0;
+      }
+    }
+    __syncthreads();   // the keys and wave_total are the next task's
+  }
+}
 }  // namespace
 
 #define SC_TRY(expr)                                                                                          \
@@ -261,12 +420,17 @@ struct ScoreState {
   int device = -1;
   uint32_t n_cu = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::mutex mu;   // one score call at a time on this replica
-  void* scratch[6] = {};   // q_off, comps, vals, tiles, candidate ids, scores
-  uint64_t scratch_bytes[6] = {};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+  std::mutex mu;   // one score or rerank call at a time on this replica
+  // q_off, comps, vals, tiles, candidate ids, scores; rerank: tasks, slots, carry slots, row scores, row ids, row counts
+  void* scratch[12] = {};
+  uint64_t scratch_bytes[12] = {};
   std::vector<uint4> tiles;     // host staging of a launch
   std::vector<uint32_t> ids;
+  std::vector<std::vector<SelTask>> sel_rounds;   // [round * tiers + tier]
+  std::vector<SelTask> sel_tasks;
+  double last_select_ms = 0;    // rerank: device time of the selection kernels, merge rounds run
+  uint32_t last_merge_rounds = 0;
   double last_kernel_ms = 0;    // device time of the last call's kernels, its launches and its lookup form (sgpu_debug_score_stats)
   uint32_t last_launches = 0, last_dense = 0, last_grid = 0, last_block = 0, last_lds = 0;
 };
@@ -278,6 +442,7 @@ void score_state_free(ScoreState* s) {
   for (void* p : s->scratch) if (p) (void)hipFree(p);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
+  if (s->ev2) (void)hipEventDestroy(s->ev2);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -291,6 +456,7 @@ static sgpu_status score_state_init(ScoreState* s, int device) {
   SC_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   SC_TRY(hipEventCreate(&s->ev0));
   SC_TRY(hipEventCreate(&s->ev1));
+  SC_TRY(hipEventCreate(&s->ev2));
   return SGPU_OK;
 }
 
@@ -317,12 +483,106 @@ static bool score_hooks_on() {
   return t && *t && *t != '0';
 }
 
+// A rerank call: what the selection needs beyond a score call (null for sgpu_score_documents).
+struct RerankCall {
+  uint32_t k = 0;
+  uint32_t chunk = kRerankChunk;   // C
+  uint32_t n_tiers = 0;
+  SelTier tiers[3];
+  int carry_cur = -1;              // the carry slot the open query's survivors lie in (-1: no query is open)
+  float* out_scores = nullptr;
+  uint64_t* out_doc_ids = nullptr;
+  uint32_t* out_n = nullptr;
+};
+
+static void rerank_setup(RerankCall* rr) {
+  uint32_t c = kRerankChunk;
+  if (score_hooks_on()) {
+    if (const char* v = std::getenv("SGPU_RERANK_CHUNK"))
+      if (*v) {
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(2, std::strtoull(v, nullptr, 10)), kRerankChunk);
+        c = 2;
+        while (2ull * c <= want) c *= 2;
+        uint32_t k2 = 1;
+        while (k2 < rr->k) k2 *= 2;
+        if (rr->k > c / 2) c = 2 * k2;   // (the fan-in floor(C / k) stays at least 2; k <= 1024: at most kRerankChunk)
+      }
+  }
+  rr->chunk = c;
+  rr->n_tiers = 0;
+  for (const SelTier& t : kSelTiers) {
+    const uint32_t cap = std::min(t.cap, c);
+    if (rr->n_tiers && rr->tiers[rr->n_tiers - 1].cap >= cap) continue;
+    rr->tiers[rr->n_tiers++] = SelTier{cap, t.team};
+  }
+}
+
+// The selection tasks of one launch - candidates [first, last) of the call, the queries from q0 on - by round and tier
+// into s->sel_rounds; returns the slots they use.
+static uint32_t rerank_plan(ScoreState* s, RerankCall* rr, const uint64_t* cand_off, uint32_t nq, uint32_t q0, uint64_t first,
+                            uint64_t last) {
+  const uint32_t k = rr->k, c = rr->chunk, fan = c / k, nt = rr->n_tiers;
+  s->sel_rounds.clear();
+  auto push = [&](uint32_t round, const SelTask& t) {
+    const uint32_t keys = t.kind == SEL_RAW ? t.n : (t.n + (t.extra != kSelNone ? 1u : 0u)) * k;
+    uint32_t tier = 0;
+    while (rr->tiers[tier].cap < keys) ++tier;   // (keys <= c = the last tier's cap)
+    if (s->sel_rounds.size() < (size_t)(round + 1) * nt) s->sel_rounds.resize((size_t)(round + 1) * nt);
+    s->sel_rounds[(size_t)round * nt + tier].push_back(t);
+  };
+  uint32_t next_slot = 0;
+  for (uint32_t q = q0; q < nq && cand_off[q] < last; ++q) {
+    const uint64_t a = std::max(cand_off[q], first), b = std::min(cand_off[q + 1], last);
+    if (a >= b) continue;
+    const bool has_carry = cand_off[q] < first, ends = cand_off[q + 1] <= last;
+    const uint32_t old_carry = has_carry ? (uint32_t)rr->carry_cur : kSelNone;
+    // (the other slot than the last one written: a launch's first part may still read that one in a later round)
+    const uint32_t new_carry = rr->carry_cur < 0 ? 0u : 1u - (uint32_t)rr->carry_cur;
+    if (!ends) rr->carry_cur = (int)new_carry;
+    SelTask t{};
+    t.extra = kSelNone;
+    const uint32_t dst_kind = ends ? SEL_TO_ROW : SEL_TO_CARRY, dst = ends ? q : new_carry;
+    const uint32_t len = (uint32_t)(b - a), m = (len + c - 1) / c, at = (uint32_t)(a - first);
+    if (m == 1 && !has_carry) {
+      t.kind = SEL_RAW, t.src = at, t.n = len, t.dst_kind = dst_kind, t.dst = dst;
+      push(0, t);
+      continue;
+    }
+    uint32_t s0 = next_slot, cnt = m, extra = old_carry;
+    next_slot += m;
+    for (uint32_t j = 0; j < m; ++j) {
+      t.kind = SEL_RAW, t.src = at + j * c, t.n = std::min(c, len - j * c), t.dst_kind = SEL_TO_SLOT, t.dst = s0 + j;
+      push(0, t);
+    }
+    t.kind = SEL_KEYS;
+    for (uint32_t round = 1;; ++round) {
+      const uint32_t e = extra != kSelNone ? 1u : 0u;
+      if (cnt + e <= fan) {
+        t.src = s0, t.n = cnt, t.extra = extra, t.dst_kind = dst_kind, t.dst = dst;
+        push(round, t);
+        break;
+      }
+      const uint32_t out0 = next_slot;
+      for (uint32_t pos = 0; pos < cnt;) {
+        const uint32_t take = std::min(fan - (pos == 0 ? e : 0u), cnt - pos);
+        t.src = s0 + pos, t.n = take, t.extra = pos == 0 ? extra : kSelNone, t.dst_kind = SEL_TO_SLOT, t.dst = next_slot++;
+        push(round, t);
+        pos += take;
+      }
+      s0 = out0, cnt = next_slot - out0, extra = kSelNone;
+    }
+  }
+  return next_slot;
+}
+
 static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
                              const float* vals, uint32_t nq, uint32_t max_nnz, const uint64_t* cand_off, const uint64_t* cand_ids,
-                             float* out_scores) {
+                             float* out_scores, RerankCall* rr = nullptr) {
   SC_TRY(hipSetDevice(s->device));
   s->last_kernel_ms = 0;
   s->last_launches = 0;
+  s->last_select_ms = 0;
+  s->last_merge_rounds = 0;
   // the lookup form: the dense table where the vocabulary fits, else the hash table sized for the call's longest query
   // (test hook SGPU_SCORE_LOOKUP: 1 = dense where it fits, 2 = hash)
   const uint64_t dense_bytes = ((h.dim + 1) * 4 + 15) & ~15ull;
@@ -371,6 +631,24 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
   s->last_block = block;
   s->last_lds = lds;
 
+  SelArgs sel{};
+  if (rr) {   // the call's rows on the device, zeroed: a selection task writes the slots it fills and the row's count
+    const uint64_t cells = (uint64_t)nq * rr->k;
+    if ((st = score_scratch(s, 8, 2ull * rr->k * 8)) != SGPU_OK || (st = score_scratch(s, 9, cells * 4)) != SGPU_OK ||
+        (st = score_scratch(s, 10, cells * 8)) != SGPU_OK || (st = score_scratch(s, 11, (uint64_t)nq * 4)) != SGPU_OK)
+      return st;
+    SC_TRY(hipMemsetAsync(s->scratch[9], 0, cells * 4, s->stream));
+    SC_TRY(hipMemsetAsync(s->scratch[10], 0, cells * 8, s->stream));
+    SC_TRY(hipMemsetAsync(s->scratch[11], 0, (uint64_t)nq * 4, s->stream));
+    sel.carry = (uint64_t*)s->scratch[8];
+    sel.row_scores = (float*)s->scratch[9];
+    sel.row_ids = (uint64_t*)s->scratch[10];
+    sel.row_n = (uint32_t*)s->scratch[11];
+    sel.k = rr->k;
+    SC_TRY(hipFuncSetAttribute((const void*)rerank_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(kRerankChunk * 8u)));
+  }
+
   // launches: consecutive tiles (a query's candidates in runs of at most tile_max) while they fit the budget
   uint32_t q = 0;
   uint64_t pos = 0;   // next candidate of the call
@@ -386,6 +664,7 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
       pos += n;
     }
     const uint64_t n_cand = pos - first;
+    const uint32_t q_first = s->tiles.front().x;
     s->ids.resize(n_cand);
     for (uint64_t i = 0; i < n_cand; ++i) s->ids[i] = (uint32_t)cand_ids[first + i];
     if ((st = score_scratch(s, 3, s->tiles.size() * sizeof(uint4))) != SGPU_OK || (st = score_scratch(s, 4, n_cand * 4)) != SGPU_OK ||
@@ -403,13 +682,77 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s->stream, a);
     SC_TRY(hipGetLastError());
     SC_TRY(hipEventRecord(s->ev1, s->stream));
-    SC_TRY(hipMemcpyAsync(out_scores + first, s->scratch[5], n_cand * 4, hipMemcpyDeviceToHost, s->stream));
+    if (!rr) {
+      SC_TRY(hipMemcpyAsync(out_scores + first, s->scratch[5], n_cand * 4, hipMemcpyDeviceToHost, s->stream));
+    } else {   // the selection over this launch's scores: one launch per round and tier, in the stream's order
+      const uint32_t n_slots = rerank_plan(s, rr, cand_off, nq, q_first, first, pos);
+      s->sel_tasks.clear();
+      for (const auto& v : s->sel_rounds) s->sel_tasks.insert(s->sel_tasks.end(), v.begin(), v.end());
+      if ((st = score_scratch(s, 6, s->sel_tasks.size() * sizeof(SelTask))) != SGPU_OK ||
+          (st = score_scratch(s, 7, (uint64_t)n_slots * rr->k * 8)) != SGPU_OK)
+        return st;
+      SC_TRY(hipMemcpyAsync(s->scratch[6], s->sel_tasks.data(), s->sel_tasks.size() * sizeof(SelTask), hipMemcpyHostToDevice,
+                            s->stream));
+      sel.scores = (const float*)s->scratch[5];
+      sel.cand = (const uint32_t*)s->scratch[4];
+      sel.slots = (uint64_t*)s->scratch[7];
+      size_t at = 0;
+      for (size_t i = 0; i < s->sel_rounds.size(); ++i) {
+        const size_t n = s->sel_rounds[i].size();
+        if (!n) continue;
+        const SelTier& tier = rr->tiers[i % rr->n_tiers];
+        const uint32_t teams = kSelBlock / tier.team;
+        sel.tasks = (const SelTask*)s->scratch[6] + at;
+        sel.n_tasks = (uint32_t)n;
+        sel.cap = tier.cap;
+        sel.team = tier.team;
+        const uint32_t sel_grid = (uint32_t)std::min<uint64_t>((n + teams - 1) / teams, (uint64_t)s->n_cu * (2048u / kSelBlock));
+        hipLaunchKernelGGL(rerank_select_kernel, dim3(sel_grid), dim3(kSelBlock), teams * tier.cap * 8u, s->stream, sel);
+        SC_TRY(hipGetLastError());
+        at += n;
+      }
+      SC_TRY(hipEventRecord(s->ev2, s->stream));
+      s->last_merge_rounds += (uint32_t)(s->sel_rounds.size() / rr->n_tiers) - 1u;
+    }
     SC_TRY(hipStreamSynchronize(s->stream));   // (the staging vectors and the scratch are the next launch's)
     float ms = 0.0f;
     SC_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->last_kernel_ms += ms;
     s->last_launches += 1;
+    if (rr) {
+      SC_TRY(hipEventElapsedTime(&ms, s->ev1, s->ev2));
+      s->last_select_ms += ms;
+    }
   }
+  if (rr) {
+    const uint64_t cells = (uint64_t)nq * rr->k;
+    SC_TRY(hipMemcpyAsync(rr->out_scores, s->scratch[9], cells * 4, hipMemcpyDeviceToHost, s->stream));
+    SC_TRY(hipMemcpyAsync(rr->out_doc_ids, s->scratch[10], cells * 8, hipMemcpyDeviceToHost, s->stream));
+    SC_TRY(hipMemcpyAsync(rr->out_n, s->scratch[11], (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+    SC_TRY(hipStreamSynchronize(s->stream));
+  }
+  return SGPU_OK;
+}
+
+// The replica's score state, made on its first score or rerank call (SGPU_EDEVICE: not uploaded / no such replica).
+static sgpu_status score_state_of(sgpu_index* idx, uint32_t replica, ScoreState** out) {
+  std::lock_guard<std::mutex> lk(idx->score_mu);
+  if (replica >= idx->replicas.size())
+    return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
+  if (idx->score.size() != idx->replicas.size()) idx->score.resize(idx->replicas.size(), nullptr);
+  if (!idx->score[replica]) {
+    ScoreState* ns = new (std::nothrow) ScoreState();
+    if (!ns) return fail(SGPU_ENOMEM, "out of host memory");
+    const sgpu_status st = score_state_init(ns, device_index_device(idx->replicas[replica]));
+    if (st != SGPU_OK) {
+      const std::string msg = last_error();
+      score_state_free(ns);
+      last_error() = msg;
+      return st;
+    }
+    idx->score[replica] = ns;
+  }
+  *out = idx->score[replica];
   return SGPU_OK;
 }
 
@@ -421,25 +764,8 @@ sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint
   const sgpu_status vst = score_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, out_scores, &max_nnz);
   if (vst != SGPU_OK) return vst;
   ScoreState* s = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(idx->score_mu);
-    if (replica >= idx->replicas.size())
-      return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
-    if (idx->score.size() != idx->replicas.size()) idx->score.resize(idx->replicas.size(), nullptr);
-    if (!idx->score[replica]) {
-      ScoreState* ns = new (std::nothrow) ScoreState();
-      if (!ns) return fail(SGPU_ENOMEM, "out of host memory");
-      const sgpu_status st = score_state_init(ns, device_index_device(idx->replicas[replica]));
-      if (st != SGPU_OK) {
-        const std::string msg = last_error();
-        score_state_free(ns);
-        last_error() = msg;
-        return st;
-      }
-      idx->score[replica] = ns;
-    }
-    s = idx->score[replica];
-  }
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
   if (nq == 0 || cand_off[nq] == 0) return SGPU_OK;
   std::lock_guard<std::mutex> lk(s->mu);
   try {
@@ -450,15 +776,49 @@ sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint
   }
 }
 
-// (test hook: what the last score call on `replica` measured - out8 = {device ms of its kernels, launches, 1 = dense
-// table / 0 = hash, grid, workgroup size, LDS bytes, 0, 0}. tools/score_probe.py)
+sgpu_status rerank_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                    const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
+                                    float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  uint32_t max_nnz = 0;
+  const sgpu_status vst =
+      rerank_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, k, out_scores, out_doc_ids, out_n, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  ScoreState* s = nullptr;
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
+  if (nq == 0) return SGPU_OK;
+  if (cand_off[nq] == 0) {   // no candidate at all: zeroed rows
+    std::fill(out_scores, out_scores + (size_t)nq * k, 0.0f);
+    std::fill(out_doc_ids, out_doc_ids + (size_t)nq * k, (uint64_t)0);
+    std::fill(out_n, out_n + nq, 0u);
+    return SGPU_OK;
+  }
+  RerankCall rr;
+  rr.k = k;
+  rr.out_scores = out_scores;
+  rr.out_doc_ids = out_doc_ids;
+  rr.out_n = out_n;
+  rerank_setup(&rr);
+  std::lock_guard<std::mutex> lk(s->mu);
+  try {
+    return score_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, max_nnz, cand_off, cand_ids,
+                     nullptr, &rr);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+// (test hook: what the last score or rerank call on `replica` measured - out8 = {device ms of its score kernels, launches,
+// 1 = dense table / 0 = hash, grid, workgroup size, LDS bytes, device ms of the selection kernels, merge rounds}.
+// tools/score_probe.py, tools/rerank_probe.py)
 bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8) {
   std::lock_guard<std::mutex> lk(idx->score_mu);
   if (replica >= idx->score.size() || !idx->score[replica]) return false;
   ScoreState* s = idx->score[replica];
   std::lock_guard<std::mutex> lk2(s->mu);
   const double v[8] = {s->last_kernel_ms, (double)s->last_launches, (double)s->last_dense, (double)s->last_grid,
-                       (double)s->last_block, (double)s->last_lds, 0.0, 0.0};
+                       (double)s->last_block, (double)s->last_lds, s->last_select_ms, (double)s->last_merge_rounds};
   for (int i = 0; i < 8; ++i) out8[i] = v[i];
   return true;
 }

@@ -1,4 +1,5 @@
-// score_host.cpp — sgpu_score_documents_host, and the argument checks it shares with the device call.
+// score_host.cpp — sgpu_score_documents_host and sgpu_rerank_documents_host, and the argument checks they share with
+// the device calls.
 //
 // The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
@@ -6,6 +7,8 @@
 // (one per thread); components it does not carry read 0.0 and are added as +-0.0, which never changes an accumulator
 // that started at +0.0. Fixed-u8 codes: the power of two val_scale is folded into the weight, as on the device.
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <new>
 #include <vector>
 
@@ -78,6 +81,85 @@ sgpu_status score_documents_host(const HostIndex& h, const uint64_t* q_off, cons
     for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
     for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) out_scores[i] = score_one(h, cand_ids[i], dense);
     for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+  }
+  return SGPU_OK;
+}
+
+// Checks 1 - 4 of sgpu_rerank_documents, in the header's order.
+sgpu_status rerank_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                              const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, const float* out_scores,
+                              const uint64_t* out_doc_ids, const uint32_t* out_n, uint32_t* max_nnz) {
+  if (!out_doc_ids || !out_n) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out_scores, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (k == 0) return fail(SGPU_EINVAL, "k must be at least 1");
+  if (k > kRerankMaxK) return fail(SGPU_ELIMIT, "k = %u (reranking documents: limit %u)", k, kRerankMaxK);
+  return SGPU_OK;
+}
+
+// The host twin of the device's selection (score_documents.hip), the arbiter of its rows: per query the distinct ids of
+// its candidates, each scored once by score_one (the scores of sgpu_score_documents_host), ordered by score descending -
+// NaN after every number - and id ascending, cut to k. -0.0 never occurs (score_documents.hip), so the numeric order is the
+// device's order of the scores' integer images.
+sgpu_status rerank_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                  const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, uint32_t num_threads,
+                                  float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n) {
+  uint32_t max_nnz = 0;
+  const sgpu_status vst = rerank_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, k, out_scores, out_doc_ids, out_n, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0) return SGPU_OK;
+  std::memset(out_scores, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out_doc_ids, 0, (size_t)nq * k * sizeof(uint64_t));
+  std::memset(out_n, 0, (size_t)nq * sizeof(uint32_t));
+  if (cand_off[nq] == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  struct Item {
+    float score;
+    uint64_t id;
+  };
+  std::vector<std::vector<float>> tables;
+  std::vector<std::vector<Item>> items;
+  uint64_t longest = 0;
+  for (uint32_t q = 0; q < nq; ++q) longest = std::max(longest, cand_off[q + 1] - cand_off[q]);
+  try {
+    tables.assign((size_t)team, std::vector<float>());
+    for (auto& t : tables) t.assign(h.dim, 0.0f);
+    items.assign((size_t)team, std::vector<Item>());
+    for (auto& v : items) v.reserve(longest);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+    if (cand_off[q + 1] == cand_off[q]) continue;
+#ifdef _OPENMP
+    const size_t me = (size_t)omp_get_thread_num();
+#else
+    const size_t me = 0;
+#endif
+    float* dense = tables[me].data();
+    std::vector<Item>& it = items[me];   // (reserved for the longest list: nothing below allocates)
+    it.clear();
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) it.push_back(Item{0.0f, cand_ids[i]});
+    std::sort(it.begin(), it.end(), [](const Item& a, const Item& b) { return a.id < b.id; });
+    it.erase(std::unique(it.begin(), it.end(), [](const Item& a, const Item& b) { return a.id == b.id; }), it.end());
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
+    for (Item& x : it) x.score = score_one(h, x.id, dense);
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+    const size_t n = std::min<size_t>(k, it.size());
+    std::partial_sort(it.begin(), it.begin() + (ptrdiff_t)n, it.end(), [](const Item& a, const Item& b) {
+      const bool na = std::isnan(a.score), nb = std::isnan(b.score);
+      if (na != nb) return nb;
+      if (!na && a.score != b.score) return a.score > b.score;
+      return a.id < b.id;
+    });
+    for (size_t i = 0; i < n; ++i) {
+      out_scores[(size_t)q * k + i] = it[i].score;
+      out_doc_ids[(size_t)q * k + i] = it[i].id;
+    }
+    out_n[q] = (uint32_t)n;
   }
   return SGPU_OK;
 }

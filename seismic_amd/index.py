@@ -314,13 +314,13 @@ class SeismicDatasetLV(_DatasetBase):
 
 # ---------------------------------------------------------------------------
 class _ScoreMixin:
-    """score / batch_score / batch_rerank of the index classes: the scores of caller-given documents
-    (sgpu_score_documents; no reference counterpart - the reference computes such a score only inside its search,
+    """score / batch_score / rerank / batch_rerank of the index classes: the scores of caller-given documents and the k
+    best of them (sgpu_score_documents, sgpu_rerank_documents; no reference counterpart - the reference computes such a score only inside its search,
     QueryEvaluator::compute_distance at src/posting_list.rs:210-211). A score is what search returns for the document,
     bit for bit. The classes supply _score_queries (queries -> CSR, unknown tokens dropped as in search),
     _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id)."""
 
-    def _batch_score_native(self, query_components, query_values, doc_ids_per_query, device):
+    def _score_csr(self, query_components, query_values, doc_ids_per_query):
         off, comps, vals = self._score_queries(query_components, query_values)
         rows = [self._score_rows(d) for d in doc_ids_per_query]
         if len(rows) != len(off) - 1:
@@ -329,13 +329,23 @@ class _ScoreMixin:
         if rows:
             cand_off[1:] = np.cumsum([len(r) for r in rows])
         cand = np.concatenate(rows).astype(np.uint64) if rows else np.zeros(0, np.uint64)
+        return off, comps, vals, cand_off, cand, rows
+
+    def _score_on_device(self, device):
+        """False: the host twin. Else the GPU the index is on (uploading it if need be)."""
         if device is False:
-            sc = self._ix.score_documents_host(off, comps, vals, cand_off, cand)
-        else:
-            if device is not None and device is not True and int(device) != int(self._device):
-                raise ValueError("the index is on device %d, not %d" % (self._device, int(device)))
-            self._ensure_device()
+            return False
+        if device is not None and device is not True and int(device) != int(self._device):
+            raise ValueError("the index is on device %d, not %d" % (self._device, int(device)))
+        self._ensure_device()
+        return True
+
+    def _batch_score_native(self, query_components, query_values, doc_ids_per_query, device):
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        if self._score_on_device(device):
             sc = self._ix.score_documents(off, comps, vals, cand_off, cand)
+        else:
+            sc = self._ix.score_documents_host(off, comps, vals, cand_off, cand)
         bounds = cand_off.astype(np.int64)
         return [sc[bounds[i]:bounds[i + 1]] for i in range(len(rows))], rows
 
@@ -350,7 +360,26 @@ class _ScoreMixin:
 
     def batch_rerank(self, query_components, query_values, doc_ids_per_query, k, device=None):
         """Per query the k best of its candidates -> [[(score, doc_id)]]: score descending, ties by native document id
-        ascending, a candidate given more than once counted once."""
+        ascending, a candidate given more than once counted once. Scored and selected by sgpu_rerank_documents on the GPU
+        the index is on (device None) or by its host twin (device False); a k the library does not take (0, above 1024)
+        is selected here from batch_score's scores."""
+        k = int(k)
+        if not 1 <= k <= 1024:
+            return self._batch_rerank_numpy(query_components, query_values, doc_ids_per_query, k, device)
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        if self._score_on_device(device):
+            sc, ids, n = self._ix.rerank_documents(off, comps, vals, cand_off, cand, k)
+        else:
+            sc, ids, n = self._ix.rerank_documents_host(off, comps, vals, cand_off, cand, k)
+        sc, ids = sc.tolist(), ids.tolist()
+        name = self._score_name
+        return [[(s, name(d)) for s, d in zip(sc[q][:m], ids[q][:m])] for q, m in enumerate(n.tolist())]
+
+    def rerank(self, query_components, query_values, doc_ids, k, device=None):
+        """The k best of the documents `doc_ids` for one query -> [(score, doc_id)], best first."""
+        return self.batch_rerank([query_components], [query_values], [doc_ids], k, device)[0]
+
+    def _batch_rerank_numpy(self, query_components, query_values, doc_ids_per_query, k, device):
         scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
         out = []
         for sc, r in zip(scores, rows):
