@@ -58,6 +58,7 @@ sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);
 sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
                                 uint32_t* out_n, const sgpu_filter* filter);
+bool exact_debug_launches(sgpu_index* idx, uint32_t replica, uint32_t* out);
 // score_documents.hip
 sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                    const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
@@ -877,6 +878,16 @@ sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* ou
   SGPU_HOOK_OR(SGPU_EINVAL);
   if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");
   if (!score_debug_stats(idx, replica, out8)) return fail(SGPU_EINVAL, "no score call has run on replica %u", replica);
+  return SGPU_OK;
+}
+
+// (not part of the boundary: the accumulate launches of the last sgpu_exact_search_device[_filtered] call on `replica`, one
+// per chunk of queries whose candidates fit the candidate buffer - 256 MiB, or what SGPU_EXACT_CAND_BYTES says; SGPU_EINVAL
+// before the replica's first exact call. tests/test_gpu_exact_edges.py)
+sgpu_status sgpu_debug_exact_launches(sgpu_index* idx, uint32_t replica, uint32_t* out_launches) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out_launches) return fail(SGPU_EINVAL, "null argument");
+  if (!exact_debug_launches(idx, replica, out_launches)) return fail(SGPU_EINVAL, "no exact call has run on replica %u", replica);
   return SGPU_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -40,7 +41,7 @@ constexpr uint32_t kE = 8;            // entries per thread and step
 constexpr uint32_t kGroup = 256;      // query components resolved to segments at a time (LDS)
 constexpr uint32_t kMergeBS = 256;    // threads of the merge kernel
 constexpr uint32_t kMaxK = 1024;
-constexpr uint64_t kCandBytes = 256ull << 20;   // candidate buffer per chunk of queries
+constexpr uint64_t kCandBytes = 256ull << 20;   // candidate buffer per chunk of queries (test hook SGPU_EXACT_CAND_BYTES lowers it)
 constexpr uint64_t kMaxTable = 1ull << 28;      // dense offset table entries (1 GiB)
 
 __device__ __forceinline__ uint32_t fkey(float x) {   // ascending with the float (NaN aside)
@@ -462,6 +463,7 @@ struct ExactFile {
   uint64_t scratch_bytes[6] = {};
   uint32_t* d_n = nullptr;
   uint64_t d_n_bytes = 0;
+  uint32_t last_launches = 0;   // accumulate launches of the last call (sgpu_debug_exact_launches)
 };
 
 void exact_file_free(ExactFile* f) {
@@ -565,11 +567,17 @@ static sgpu_status scratch(ExactFile* f, int i, uint64_t bytes) {
   return st;
 }
 
+static bool exact_hooks_on() {
+  const char* t = std::getenv("SGPU_TEST_HOOKS");
+  return t && *t && *t != '0';
+}
+
 // (bits: a filter's allowed set on this device and its size n_allowed, or null)
 static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                              uint32_t k, float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* bits,
                              uint64_t n_allowed) {
   EX_TRY(hipSetDevice(f->device));
+  f->last_launches = 0;
   const uint32_t out_nn = (uint32_t)std::min<uint64_t>(k, bits ? n_allowed : f->n_docs);
   if (f->n_ranges == 0) {   // (no documents: nothing to return)
     for (uint32_t q = 0; q < nq; ++q) out_n[q] = 0;
@@ -577,7 +585,12 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
   }
   const uint64_t qnnz = q_off[nq];
   const uint64_t per_q = (uint64_t)f->n_ranges * k * 8;
-  const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, kCandBytes / per_q));
+  // (test hook SGPU_EXACT_CAND_BYTES, read per call: a smaller candidate buffer, so that a few queries are several chunks)
+  uint64_t cand_bytes = kCandBytes;
+  if (exact_hooks_on())
+    if (const char* v = std::getenv("SGPU_EXACT_CAND_BYTES"))
+      if (*v) cand_bytes = std::min<uint64_t>(std::max<uint64_t>(1, std::strtoull(v, nullptr, 10)), kCandBytes);
+  const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, cand_bytes / per_q));
   sgpu_status st;
   if ((st = scratch(f, 0, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = scratch(f, 1, qnnz * 4)) != SGPU_OK ||
       (st = scratch(f, 2, qnnz * 4)) != SGPU_OK || (st = scratch(f, 3, (uint64_t)chunk * per_q)) != SGPU_OK ||
@@ -619,6 +632,7 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
     const uint32_t grid = (uint32_t)std::min<uint64_t>(tasks, f->n_cu);
     hipLaunchKernelGGL(exact_accumulate_kernel, dim3(grid), dim3(kBS), 0, f->stream, a);
     EX_TRY(hipGetLastError());
+    ++f->last_launches;
     hipLaunchKernelGGL(exact_merge_kernel, dim3(n), dim3(kMergeBS), 0, f->stream, (const uint64_t*)a.cand, f->n_ranges,
                        k, out_nn, q0, (float*)f->scratch[4], (uint64_t*)f->scratch[5], f->d_n);
     EX_TRY(hipGetLastError());
@@ -674,6 +688,19 @@ sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_
   if (nq == 0) return SGPU_OK;
   std::lock_guard<std::mutex> lk(f->mu);
   return exact_run(f, q_off, comps, vals, nq, k, out_scores, out_ids, out_n, fv ? fv->bits : nullptr, fv ? fv->count : 0);
+}
+
+// (test hook: the accumulate launches - chunks of queries - of the last exact call on `replica`; false before its first)
+bool exact_debug_launches(sgpu_index* idx, uint32_t replica, uint32_t* out) {
+  ExactFile* f = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(idx->exact_mu);
+    if (replica >= idx->exact.size() || !idx->exact[replica]) return false;
+    f = idx->exact[replica];
+  }
+  std::lock_guard<std::mutex> lk(f->mu);
+  *out = f->last_launches;
+  return true;
 }
 
 }  // namespace sgpu
