@@ -409,8 +409,7 @@ static sgpu_status search_segment(DeviceIndex* d, uint64_t dim, const uint64_t* 
   }();
   // (SGPU_CHUNK_FIRST, a test hook: the first chunk's share of a call in per mille; unset or 0: equal chunks)
   static const uint32_t chunk_first_pm = [] {
-    const char* t = std::getenv("SGPU_TEST_HOOKS");
-    const char* v = (t && *t && *t != '0') ? std::getenv("SGPU_CHUNK_FIRST") : nullptr;
+    const char* v = test_hooks_on() ? std::getenv("SGPU_CHUNK_FIRST") : nullptr;
     return v && *v ? (uint32_t)std::strtoul(v, nullptr, 10) : 0u;
   }();
   const uint32_t nq = s1 - s0;
@@ -671,10 +670,6 @@ sgpu_status sgpu_search_sequential(sgpu_index* idx, const uint64_t* q_off, const
 // Entry points the test suite and the tools use to look at host-side decisions (team size, chunk plan, launch plan,
 // packed records, phase clocks, cooperative trace). Like the undocumented environment names they are inert unless
 // SGPU_TEST_HOOKS=1 is set: status-returning ones fail with SGPU_EINVAL, the others return 0 / do nothing.
-static bool test_hooks_on() {
-  const char* t = std::getenv("SGPU_TEST_HOOKS");
-  return t && *t && *t != '0';
-}
 #define SGPU_HOOK_OR(ret)                                                                            \
   if (!test_hooks_on()) {                                                                            \
     (void)fail(SGPU_EINVAL, "%s is a test hook: set SGPU_TEST_HOOKS=1 (include/seismic_hip_testing.h)", __func__); \

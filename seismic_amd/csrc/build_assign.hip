@@ -24,15 +24,10 @@
 #include <vector>
 
 #include "build_device.hpp"
+#include "device_prims.hpp"
+#include "hip_util.hpp"
 
 namespace sgpu {
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 constexpr int kAssignThreads = 256;            // 4 wavefronts per workgroup, a document each
 constexpr uint32_t kAssignMaxCentroids = 8192;  // accumulators of a wavefront: up to 32 KB of LDS (r04: 8192; lists of n_postings 6000 x max_fraction 4 x centroid_fraction 0.2 = 4800 centroids stayed on the host, 25 s)
@@ -69,17 +64,6 @@ struct AssignView {
 __device__ __forceinline__ uint32_t comp_of(const AssignView& v, uint64_t i) {
   return v.comp_width == 2 ? (uint32_t)((const uint16_t*)v.doc_comp)[i] : ((const uint32_t*)v.doc_comp)[i];
 }
-__device__ __forceinline__ float half_to_float(uint16_t h) {
-  _Float16 x;
-  __builtin_memcpy(&x, &h, 2);
-  return (float)x;
-}
-// f32::total_cmp order as an unsigned key
-__device__ __forceinline__ uint32_t order_key(float f) {
-  int32_t b = __float_as_int(f);
-  b ^= (int32_t)(((uint32_t)(b >> 31)) >> 1);
-  return (uint32_t)b ^ 0x80000000u;
-}
 
 // The centroid with the largest (score by total_cmp, index) among the non-avoided ones - Rust's
 // max_by keeps the LAST maximum (src/utils.rs:135-141) - or centroid 0 when every one is avoided.
@@ -88,7 +72,7 @@ __device__ __forceinline__ uint32_t best_centroid(const float* scores, const uin
   unsigned long long best = 0ull;   // (key + 1) << 32 | cid; 0 = none
   for (uint32_t c = lane; c < nc; c += 64) {
     if (avoided_bits && ((avoided_bits[c >> 5] >> (c & 31)) & 1u)) continue;
-    const unsigned long long k = (((unsigned long long)order_key(scores[c]) + 1ull) << 32) | c;
+    const unsigned long long k = (((unsigned long long)ordered_u32(scores[c]) + 1ull) << 32) | c;
     best = k > best ? k : best;
   }
 #pragma unroll
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(kAssignThreads) void assign_clusters_kernel(AssignV
         const uint32_t comp = comp_of(v, i);
         const uint32_t p = pos[comp] + atomicAdd(&cur[comp], 1u);
         inv_cid[p] = cid;
-        inv_val[p] = half_to_float(v.doc_val[i]);
+        inv_val[p] = half_bits_to_float(v.doc_val[i]);
       }
     }
     __threadfence_block();

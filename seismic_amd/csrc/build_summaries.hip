@@ -23,15 +23,10 @@
 #include <vector>
 
 #include "build_device.hpp"
+#include "device_prims.hpp"
+#include "hip_util.hpp"
 
 namespace sgpu {
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 constexpr int kSumThreads = 256;
 constexpr uint32_t kSumCap = 4096;   // entries of a block: two key buffers of 32 KB in LDS
@@ -58,41 +53,6 @@ struct SumView {
   unsigned long long* cursor;
   uint32_t* queue;
 };
-
-__device__ __forceinline__ uint32_t okey(float f) {   // f32::total_cmp order as an unsigned key
-  int32_t b = __float_as_int(f);
-  b ^= (int32_t)(((uint32_t)(b >> 31)) >> 1);
-  return (uint32_t)b ^ 0x80000000u;
-}
-__device__ __forceinline__ float okey_inv(uint32_t k) {
-  int32_t b = (int32_t)(k ^ 0x80000000u);
-  b ^= (int32_t)(((uint32_t)(b >> 31)) >> 1);
-  return __int_as_float(b);
-}
-__device__ __forceinline__ float h2f(uint16_t h) {
-  _Float16 x;
-  __builtin_memcpy(&x, &h, 2);
-  return (float)x;
-}
-
-// ascending bitonic sort of keys[0 .. p2), p2 a power of two, by the whole workgroup
-__device__ void bitonic(unsigned long long* keys, uint32_t p2) {
-  for (uint32_t size = 2; size <= p2; size <<= 1) {
-    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-      for (uint32_t t = threadIdx.x; t < p2 / 2; t += kSumThreads) {
-        const uint32_t i = 2 * t - (t & (stride - 1));
-        const uint32_t j = i + stride;
-        const bool up = (i & size) == 0;
-        const unsigned long long a = keys[i], b = keys[j];
-        if ((a > b) == up) {
-          keys[i] = b;
-          keys[j] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 __global__ __launch_bounds__(kSumThreads) void block_summaries_kernel(SumView v) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long smem_keys[];   // two buffers of kSumCap keys
@@ -122,23 +82,18 @@ __global__ __launch_bounds__(kSumThreads) void block_summaries_kernel(SumView v)
       uint32_t pos = atomicAdd(&s_cnt, (uint32_t)(e1 - e0));
       for (uint64_t i = e0; i < e1; ++i, ++pos) {
         const uint32_t c = v.comp_width == 2 ? (uint32_t)((const uint16_t*)v.doc_comp)[i] : ((const uint32_t*)v.doc_comp)[i];
-        A[pos] = ((unsigned long long)c << 32) | (unsigned long long)(~okey(h2f(v.doc_val[i])));
+        A[pos] = ((unsigned long long)c << 32) | (unsigned long long)(~ordered_u32(half_bits_to_float(v.doc_val[i])));
       }
     }
     for (uint32_t i = n + threadIdx.x; i < p2; i += kSumThreads) A[i] = ~0ull;
     __syncthreads();
-    bitonic(A, p2);
+    bitonic_sort_lds<false>(A, p2, threadIdx.x, kSumThreads);
     // ---- the maximum of every component (head of its run) -> B as (~key(value) << 32) | component
     constexpr uint32_t PER = kSumCap / kSumThreads;   // consecutive elements per thread
     const uint32_t i0 = threadIdx.x * PER;
     uint32_t heads = 0;
     for (uint32_t i = i0; i < i0 + PER && i < n; ++i) heads += (i == 0 || (uint32_t)(A[i] >> 32) != (uint32_t)(A[i - 1] >> 32));
-    uint32_t incl = heads;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(incl, d);
-      if ((int)lane >= d) incl += o;
-    }
+    const uint32_t incl = wave_incl_scan(heads);
     if (lane == 63) s_part[wave] = incl;
     __syncthreads();
     uint32_t base = 0, m = 0;
@@ -157,16 +112,16 @@ __global__ __launch_bounds__(kSumThreads) void block_summaries_kernel(SumView v)
     __syncthreads();
     for (uint32_t i = m + threadIdx.x; i < q2; i += kSumThreads) B[i] = ~0ull;
     __syncthreads();
-    bitonic(B, q2);   // value descending (by total_cmp), component ascending: the reference's sort (src/posting_list.rs:347-351)
+    bitonic_sort_lds<false>(B, q2, threadIdx.x, kSumThreads);   // value descending (by total_cmp), component ascending: the reference's sort (src/posting_list.rs:347-351)
     // ---- the energy cut: two SEQUENTIAL running sums, as the reference computes them
     if (threadIdx.x == 0) {
       float tot = 0.0f;
-      for (uint32_t i = 0; i < m; ++i) tot = __fadd_rn(tot, okey_inv(~(uint32_t)(B[i] >> 32)));
+      for (uint32_t i = 0; i < m; ++i) tot = __fadd_rn(tot, ordered_u32_inv(~(uint32_t)(B[i] >> 32)));
       const float until = __fmul_rn(tot, v.energy);
       float acc = 0.0f;
       uint32_t keep = 0;
       while (keep < m) {   // take_while_inclusive
-        acc = __fadd_rn(acc, okey_inv(~(uint32_t)(B[keep] >> 32)));
+        acc = __fadd_rn(acc, ordered_u32_inv(~(uint32_t)(B[keep] >> 32)));
         ++keep;
         if (!(acc < until)) break;
       }
@@ -178,7 +133,7 @@ __global__ __launch_bounds__(kSumThreads) void block_summaries_kernel(SumView v)
     uint32_t kmin = 0xffffffffu, kmax = 0;
     for (uint32_t i = threadIdx.x; i < keep; i += kSumThreads) {
       const uint32_t k = ~(uint32_t)(B[i] >> 32);
-      A[i] = ((B[i] & 0xffffffffull) << 32) | (unsigned long long)__float_as_uint(okey_inv(k));
+      A[i] = ((B[i] & 0xffffffffull) << 32) | (unsigned long long)__float_as_uint(ordered_u32_inv(k));
       kmin = k < kmin ? k : kmin;
       kmax = k > kmax ? k : kmax;
     }
@@ -188,8 +143,8 @@ __global__ __launch_bounds__(kSumThreads) void block_summaries_kernel(SumView v)
     atomicMin(&s_kmin, kmin);
     atomicMax(&s_kmax, kmax);
     __syncthreads();
-    bitonic(A, r2);
-    const float mn = okey_inv(s_kmin), mx = okey_inv(s_kmax);
+    bitonic_sort_lds<false>(A, r2, threadIdx.x, kSumThreads);
+    const float mn = ordered_u32_inv(s_kmin), mx = ordered_u32_inv(s_kmax);
     const float quant = __fdiv_rn(__fsub_rn(mx, mn), 255.0f);   // src/utils.rs:75
     __shared__ unsigned long long s_pos;
     if (threadIdx.x == 0) {

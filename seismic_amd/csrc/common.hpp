@@ -14,6 +14,10 @@ namespace sgpu {
 std::string& last_error();
 sgpu_status fail(sgpu_status st, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// SGPU_TEST_HOOKS=1 is set: the debug entry points (include/seismic_hip_testing.h) and the undocumented SGPU_*
+// environment names are honoured; without it they are inert. Read from the environment at every call.
+bool test_hooks_on();
+
 // Threads a host-parallel phase uses when the caller passes num_threads == 0 ("all cores", the reference's rayon
 // default): the hardware threads this process may run on, capped by the container's CPU quota (cgroup cpu.max /
 // cfs_quota_us) - a team larger than the quota is descheduled for most of every accounting period. SGPU_HOST_THREADS

@@ -14,6 +14,7 @@
 
 #include "device_types.hpp"
 #include "filter.hpp"
+#include "hip_util.hpp"
 #include "host_index.hpp"
 
 namespace sgpu {
@@ -47,18 +48,8 @@ static hipError_t run_any(const LaunchArgs& a, int* occ) {
 hipError_t occupancy_search(const LaunchArgs& a, int* blocks_per_cu) { return run_any(a, blocks_per_cu); }
 hipError_t launch_search(const LaunchArgs& a) { return run_any(a, nullptr); }
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
 // (a test hook read outside the per-call knob cache: only while SGPU_TEST_HOOKS=1 is set; see hooks_on below)
-static const char* hook_raw(const char* name) {
-  const char* t = std::getenv("SGPU_TEST_HOOKS");
-  return (t && *t && *t != '0') ? std::getenv(name) : nullptr;
-}
+static const char* hook_raw(const char* name) { return test_hooks_on() ? std::getenv(name) : nullptr; }
 
 }  // namespace sgpu
 struct sgpu_batch;

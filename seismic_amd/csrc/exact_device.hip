@@ -25,13 +25,11 @@
 #include <new>
 #include <vector>
 
+#include "device_prims.hpp"
 #include "filter.hpp"
-#include "host_index.hpp"
+#include "hip_util.hpp"
 
 namespace sgpu {
-
-// (device_index.hip)
-int device_index_device(const DeviceIndex* d);
 
 namespace {
 
@@ -43,29 +41,6 @@ constexpr uint32_t kMergeBS = 256;    // threads of the merge kernel
 constexpr uint32_t kMaxK = 1024;
 constexpr uint64_t kCandBytes = 256ull << 20;   // candidate buffer per chunk of queries (test hook SGPU_EXACT_CAND_BYTES lowers it)
 constexpr uint64_t kMaxTable = 1ull << 28;      // dense offset table entries (1 GiB)
-
-__device__ __forceinline__ uint32_t fkey(float x) {   // ascending with the float (NaN aside)
-  const uint32_t b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ float half_bits_to_f32(uint32_t h) {   // exact binary16 -> binary32 (v_cvt_f32_f16)
-  const unsigned short b = (unsigned short)h;
-  _Float16 x;
-  __builtin_memcpy(&x, &b, 2);
-  return (float)x;
-}
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const uint32_t lane = __lane_id();
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 
 // ---- build -----------------------------------------------------------------------------------------------------
 // one wave per document; every (range, component) pair of the forward index counted
@@ -225,7 +200,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
           const uint32_t x = cur[i];
           if (x != 0xffffffffu) {
             const uint32_t l = x & 0xffffu;
-            const float w = a.f16 ? half_bits_to_f32(x >> 16) : __fmul_rn((float)(x >> 16), a.val_scale);
+            const float w = a.f16 ? half_bits_to_float(x >> 16) : __fmul_rn((float)(x >> 16), a.val_scale);
             acc[l] = __fadd_rn(acc[l], __fmul_rn(qv, w));
           }
         }
@@ -238,7 +213,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
     }
     __syncthreads();
 
-    // ---- the task's top-k over all its documents: key = fkey(score) << 16 | (0xffff - local), larger is better
+    // ---- the task's top-k over all its documents: key = ordered_u32(score) << 16 | (0xffff - local), larger is better
     const uint64_t d0 = (uint64_t)r * kRange;
     const uint32_t nr = (uint32_t)min<uint64_t>(kRange, a.n_docs - d0);
     uint64_t* out = a.cand + task * a.k;
@@ -264,13 +239,13 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
     if (n_ok <= a.k) {
       if (!a.bits) {
         for (uint32_t l = tid; l < a.k; l += kBS)
-          out[l] = l < nr ? ((uint64_t)fkey(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l)) : 0ull;
+          out[l] = l < nr ? ((uint64_t)ordered_u32(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l)) : 0ull;
         continue;
       }
       if (tid == 0) s_sel[3] = 0;
       __syncthreads();
       for (uint32_t l = tid; l < nr; l += kBS)
-        if (candidate(l)) out[atomicAdd(&s_sel[3], 1u)] = ((uint64_t)fkey(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l));
+        if (candidate(l)) out[atomicAdd(&s_sel[3], 1u)] = ((uint64_t)ordered_u32(acc[l]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)(d0 + l));
       for (uint32_t l = n_ok + tid; l < a.k; l += kBS) out[l] = 0ull;
       continue;
     }
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
 #pragma unroll
         for (uint32_t e = 0; e < 4; ++e) {
           const uint32_t l = l0 + e;
-          const uint64_t key = ((uint64_t)fkey(vs[e]) << 16) | (uint64_t)(0xffffu - l);
+          const uint64_t key = ((uint64_t)ordered_u32(vs[e]) << 16) | (uint64_t)(0xffffu - l);
           if (candidate(l) && (key & mask) == prefix) {
             const uint32_t bin = (uint32_t)(key >> shift) & 255u;
             if (bin == run_bin) {
@@ -302,28 +277,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
       }
       if (run_n) atomicAdd(&hist[run_bin], run_n);
       __syncthreads();
-      if (tid < 64) {   // the bin where the running count from the top reaches `need`
-        uint32_t h[4], s = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-          h[i] = hist[255 - 4 * lane - i];
-          s += h[i];
-        }
-        const uint32_t incl = wave_incl_scan(s);
-        uint32_t above = incl - s;
-        if (above < need && need <= incl) {
-#pragma unroll
-          for (uint32_t i = 0; i < 4; ++i) {
-            if (above < need && need <= above + h[i]) {
-              s_sel[0] = 255 - 4 * lane - i;
-              s_sel[1] = need - above;
-              s_sel[2] = h[i];
-            }
-            above += h[i];
-          }
-        }
-        s_sel[3] = 0;
-      }
+      if (tid < 64) radix_select_pick(hist, need, lane, s_sel);   // the bin where the running count from the top reaches `need`
       __syncthreads();
       const uint32_t b = s_sel[0], hb = s_sel[2];
       need = s_sel[1];
@@ -339,7 +293,7 @@ __global__ __launch_bounds__(kBS) void exact_accumulate_kernel(AccArgs a) {
 #pragma unroll
       for (uint32_t e = 0; e < 4; ++e) {
         const uint32_t l = l0 + e;
-        const uint32_t fk = fkey(vs[e]);
+        const uint32_t fk = ordered_u32(vs[e]);
         const uint64_t key = ((uint64_t)fk << 16) | (uint64_t)(0xffffu - l);
         if (candidate(l) && (key & mask) >= prefix) {
           const uint32_t slot = atomicAdd(&s_sel[3], 1u);
@@ -370,28 +324,7 @@ __global__ __launch_bounds__(kMergeBS) void exact_merge_kernel(const uint64_t* _
       if ((key & mask) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
     }
     __syncthreads();
-    if (tid < 64) {
-      uint32_t h[4], s = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i) {
-        h[i] = hist[255 - 4 * lane - i];
-        s += h[i];
-      }
-      const uint32_t incl = wave_incl_scan(s);
-      uint32_t above = incl - s;
-      if (above < need && need <= incl) {
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-          if (above < need && need <= above + h[i]) {
-            s_sel[0] = 255 - 4 * lane - i;
-            s_sel[1] = need - above;
-            s_sel[2] = h[i];
-          }
-          above += h[i];
-        }
-      }
-      s_sel[3] = 0;
-    }
+    if (tid < 64) radix_select_pick(hist, need, lane, s_sel);
     __syncthreads();
     const uint32_t b = s_sel[0], hb = s_sel[2];
     need = s_sel[1];
@@ -414,37 +347,17 @@ __global__ __launch_bounds__(kMergeBS) void exact_merge_kernel(const uint64_t* _
       }
     }
   __syncthreads();
-  // bitonic sort, descending
-  for (uint32_t size = 2; size <= p2; size <<= 1)
-    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-      for (uint32_t i = tid; i < p2 / 2; i += kMergeBS) {
-        const uint32_t lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const uint64_t x = sel[lo], y = sel[hi];
-        if ((x < y) == desc) {
-          sel[lo] = y;
-          sel[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_lds<true>(sel, p2, tid, kMergeBS);
   const uint64_t row = (uint64_t)(q0 + blockIdx.x) * k;
   for (uint32_t i = tid; i < k; i += kMergeBS) {
     const uint64_t key = i < out_n ? sel[i] : 0ull;
-    out_scores[row + i] = i < out_n ? fkey_inv((uint32_t)(key >> 32)) : 0.0f;
+    out_scores[row + i] = i < out_n ? ordered_u32_inv((uint32_t)(key >> 32)) : 0.0f;
     out_ids[row + i] = i < out_n ? (uint64_t)(0xffffffffu - (uint32_t)key) : 0ull;
   }
   if (tid == 0) out_nq[q0 + blockIdx.x] = out_n;
 }
 
 }  // namespace
-
-#define EX_TRY(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess)                                                                                     \
-      return fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 struct ExactFile {
   int device = -1;
@@ -453,16 +366,11 @@ struct ExactFile {
   uint64_t n_docs = 0, dim = 0;
   uint32_t n_ranges = 0, f16 = 1;
   float val_scale = 0.0f;
-  uint32_t* ent = nullptr;
-  uint32_t* off = nullptr;
-  uint64_t* rbase = nullptr;
+  DeviceBuffer ent, off, rbase;   // the file: u32 entries, u32 offsets [range][dim + 1], u64 base per range
   uint64_t bytes = 0;
   std::mutex mu;   // one exact call at a time on this file (its stream and scratch)
-  // per-call scratch, grown as calls need it
-  void* scratch[6] = {};   // q_off, comps, vals, candidates, scores, ids
-  uint64_t scratch_bytes[6] = {};
-  uint32_t* d_n = nullptr;
-  uint64_t d_n_bytes = 0;
+  // per-call scratch, grown as calls need it: the staged queries, the chunk's candidates, the call's result rows
+  DeviceBuffer q_off, q_comp, q_val, cand, out_scores, out_ids, out_n;
   uint32_t last_launches = 0;   // accumulate launches of the last call (sgpu_debug_exact_launches)
 };
 
@@ -470,20 +378,13 @@ void exact_file_free(ExactFile* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  for (void* p : {(void*)f->ent, (void*)f->off, (void*)f->rbase, (void*)f->d_n}) if (p) (void)hipFree(p);
-  for (void* p : f->scratch) if (p) (void)hipFree(p);
+  for (DeviceBuffer* b : {&f->ent, &f->off, &f->rbase, &f->q_off, &f->q_comp, &f->q_val, &f->cand, &f->out_scores, &f->out_ids, &f->out_n})
+    b->release();
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;
 }
 
-static sgpu_status ex_alloc(void** p, uint64_t bytes) {
-  if (hipMalloc(p, std::max<uint64_t>(bytes, 16)) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail(SGPU_ENOMEM, "out of device memory for exact search (%llu bytes)", (unsigned long long)bytes);
-  }
-  return SGPU_OK;
-}
+static sgpu_status ex_reserve(ExactFile* f, DeviceBuffer& b, uint64_t bytes) { return b.reserve(f->stream, bytes, "for exact search"); }
 
 // Builds the file of `h` on `device` (histogram, scan, scatter on the device, from the uploaded forward arrays).
 static sgpu_status exact_file_build_on(const HostIndex& h, int device, ExactFile* f) {
@@ -502,49 +403,49 @@ static sgpu_status exact_file_build_on(const HostIndex& h, int device, ExactFile
   f->n_ranges = (uint32_t)n_ranges;
   f->f16 = h.value_type == SGPU_VAL_F16;
   f->val_scale = h.val_scale;
-  EX_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   int n_cu = 0;
-  EX_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
   f->n_cu = (uint32_t)std::max(n_cu, 1);
-  EX_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
   sgpu_status st;
   const uint64_t table = n_ranges * dim1;
-  if ((st = ex_alloc((void**)&f->ent, nnz * 4)) != SGPU_OK) return st;
-  if ((st = ex_alloc((void**)&f->off, table * 4)) != SGPU_OK) return st;
-  if ((st = ex_alloc((void**)&f->rbase, (n_ranges + 1) * 8)) != SGPU_OK) return st;
+  if ((st = ex_reserve(f, f->ent, nnz * 4)) != SGPU_OK || (st = ex_reserve(f, f->off, table * 4)) != SGPU_OK ||
+      (st = ex_reserve(f, f->rbase, (n_ranges + 1) * 8)) != SGPU_OK)
+    return st;
   f->bytes = nnz * 4 + table * 4 + (n_ranges + 1) * 8;
   // the forward arrays, and the counts (then the scatter's cursor): freed once the file is built
-  void* tmp[4] = {};
+  DeviceBuffer fwd_off, fwd_comp, fwd_val, cnt;
   auto release = [&]() {
     (void)hipStreamSynchronize(f->stream);
-    for (void* p : tmp) if (p) (void)hipFree(p);
+    for (DeviceBuffer* b : {&fwd_off, &fwd_comp, &fwd_val, &cnt}) b->release();
   };
   const uint32_t vb = h.val_bytes();
-  if ((st = ex_alloc(&tmp[0], (h.n_docs + 1) * 8)) != SGPU_OK ||
-      (st = ex_alloc(&tmp[1], nnz * h.comp_width)) != SGPU_OK || (st = ex_alloc(&tmp[2], nnz * vb)) != SGPU_OK ||
-      (st = ex_alloc(&tmp[3], table * 4)) != SGPU_OK) {
+  if ((st = ex_reserve(f, fwd_off, (h.n_docs + 1) * 8)) != SGPU_OK || (st = ex_reserve(f, fwd_comp, nnz * h.comp_width)) != SGPU_OK ||
+      (st = ex_reserve(f, fwd_val, nnz * vb)) != SGPU_OK || (st = ex_reserve(f, cnt, table * 4)) != SGPU_OK) {
     release();
     return st;
   }
   const void* vals = h.value_type == SGPU_VAL_F16 ? (const void*)h.fwd_vals.data() : (const void*)h.fwd_codes.data();
-  hipError_t e = hipMemcpyAsync(tmp[0], h.fwd_offsets.data(), (h.n_docs + 1) * 8, hipMemcpyHostToDevice, f->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(tmp[1], h.fwd_comps.data(), nnz * h.comp_width, hipMemcpyHostToDevice, f->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(tmp[2], vals, nnz * vb, hipMemcpyHostToDevice, f->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(f->rbase, rbase.data(), (n_ranges + 1) * 8, hipMemcpyHostToDevice, f->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(tmp[3], 0, table * 4, f->stream);
+  hipError_t e = hipMemcpyAsync(fwd_off.p, h.fwd_offsets.data(), (h.n_docs + 1) * 8, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(fwd_comp.p, h.fwd_comps.data(), nnz * h.comp_width, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(fwd_val.p, vals, nnz * vb, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(f->rbase.p, rbase.data(), (n_ranges + 1) * 8, hipMemcpyHostToDevice, f->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, table * 4, f->stream);
   const uint32_t grid = std::max<uint32_t>(1, (uint32_t)std::min<uint64_t>((h.n_docs + 3) / 4, 64ull * f->n_cu));
   if (e == hipSuccess && h.n_docs) {
-    hipLaunchKernelGGL(exact_count_kernel, dim3(grid), dim3(256), 0, f->stream, (const uint64_t*)tmp[0],
-                       (const uint8_t*)tmp[1], h.comp_width, h.n_docs, dim1, (uint32_t*)tmp[3]);
+    hipLaunchKernelGGL(exact_count_kernel, dim3(grid), dim3(256), 0, f->stream, fwd_off.as<const uint64_t>(),
+                       fwd_comp.as<const uint8_t>(), h.comp_width, h.n_docs, dim1, cnt.as<uint32_t>());
     e = hipGetLastError();
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(exact_scan_kernel, dim3((uint32_t)n_ranges), dim3(1024), 0, f->stream, (uint32_t*)tmp[3], f->off, dim1);
+      hipLaunchKernelGGL(exact_scan_kernel, dim3((uint32_t)n_ranges), dim3(1024), 0, f->stream, cnt.as<uint32_t>(),
+                         f->off.as<uint32_t>(), dim1);
       e = hipGetLastError();
     }
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(exact_scatter_kernel, dim3(grid), dim3(256), 0, f->stream, (const uint64_t*)tmp[0],
-                         (const uint8_t*)tmp[1], (const uint8_t*)tmp[2], h.comp_width, f->f16, h.n_docs, dim1,
-                         (const uint64_t*)f->rbase, (uint32_t*)tmp[3], f->ent);
+      hipLaunchKernelGGL(exact_scatter_kernel, dim3(grid), dim3(256), 0, f->stream, fwd_off.as<const uint64_t>(),
+                         fwd_comp.as<const uint8_t>(), fwd_val.as<const uint8_t>(), h.comp_width, f->f16, h.n_docs, dim1,
+                         f->rbase.as<const uint64_t>(), cnt.as<uint32_t>(), f->ent.as<uint32_t>());
       e = hipGetLastError();
     }
   }
@@ -554,29 +455,11 @@ static sgpu_status exact_file_build_on(const HostIndex& h, int device, ExactFile
   return SGPU_OK;
 }
 
-static sgpu_status scratch(ExactFile* f, int i, uint64_t bytes) {
-  if (f->scratch_bytes[i] >= bytes && f->scratch[i]) return SGPU_OK;
-  if (f->scratch[i]) {
-    (void)hipStreamSynchronize(f->stream);
-    (void)hipFree(f->scratch[i]);
-    f->scratch[i] = nullptr;
-    f->scratch_bytes[i] = 0;
-  }
-  const sgpu_status st = ex_alloc(&f->scratch[i], bytes);
-  if (st == SGPU_OK) f->scratch_bytes[i] = std::max<uint64_t>(bytes, 16);
-  return st;
-}
-
-static bool exact_hooks_on() {
-  const char* t = std::getenv("SGPU_TEST_HOOKS");
-  return t && *t && *t != '0';
-}
-
 // (bits: a filter's allowed set on this device and its size n_allowed, or null)
 static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                              uint32_t k, float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* bits,
                              uint64_t n_allowed) {
-  EX_TRY(hipSetDevice(f->device));
+  HIP_TRY(hipSetDevice(f->device));
   f->last_launches = 0;
   const uint32_t out_nn = (uint32_t)std::min<uint64_t>(k, bits ? n_allowed : f->n_docs);
   if (f->n_ranges == 0) {   // (no documents: nothing to return)
@@ -587,42 +470,35 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
   const uint64_t per_q = (uint64_t)f->n_ranges * k * 8;
   // (test hook SGPU_EXACT_CAND_BYTES, read per call: a smaller candidate buffer, so that a few queries are several chunks)
   uint64_t cand_bytes = kCandBytes;
-  if (exact_hooks_on())
+  if (test_hooks_on())
     if (const char* v = std::getenv("SGPU_EXACT_CAND_BYTES"))
       if (*v) cand_bytes = std::min<uint64_t>(std::max<uint64_t>(1, std::strtoull(v, nullptr, 10)), kCandBytes);
   const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, cand_bytes / per_q));
   sgpu_status st;
-  if ((st = scratch(f, 0, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = scratch(f, 1, qnnz * 4)) != SGPU_OK ||
-      (st = scratch(f, 2, qnnz * 4)) != SGPU_OK || (st = scratch(f, 3, (uint64_t)chunk * per_q)) != SGPU_OK ||
-      (st = scratch(f, 4, (uint64_t)nq * k * 4)) != SGPU_OK || (st = scratch(f, 5, (uint64_t)nq * k * 8)) != SGPU_OK)
+  if ((st = ex_reserve(f, f->q_off, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = ex_reserve(f, f->q_comp, qnnz * 4)) != SGPU_OK ||
+      (st = ex_reserve(f, f->q_val, qnnz * 4)) != SGPU_OK || (st = ex_reserve(f, f->cand, (uint64_t)chunk * per_q)) != SGPU_OK ||
+      (st = ex_reserve(f, f->out_scores, (uint64_t)nq * k * 4)) != SGPU_OK ||
+      (st = ex_reserve(f, f->out_ids, (uint64_t)nq * k * 8)) != SGPU_OK || (st = ex_reserve(f, f->out_n, (uint64_t)nq * 4)) != SGPU_OK)
     return st;
-  if (f->d_n_bytes < (uint64_t)nq * 4 || !f->d_n) {
-    if (f->d_n) (void)hipFree(f->d_n);
-    f->d_n = nullptr;
-    f->d_n_bytes = 0;
-    if ((st = ex_alloc((void**)&f->d_n, (uint64_t)nq * 4)) != SGPU_OK) return st;
-    f->d_n_bytes = std::max<uint64_t>((uint64_t)nq * 4, 16);
-  }
-  uint64_t* d_qoff = (uint64_t*)f->scratch[0];
-  EX_TRY(hipMemcpyAsync(d_qoff, q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipMemcpyAsync(f->q_off.p, q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, f->stream));
   if (qnnz) {
-    EX_TRY(hipMemcpyAsync(f->scratch[1], comps, qnnz * 4, hipMemcpyHostToDevice, f->stream));
-    EX_TRY(hipMemcpyAsync(f->scratch[2], vals, qnnz * 4, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(f->q_comp.p, comps, qnnz * 4, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(f->q_val.p, vals, qnnz * 4, hipMemcpyHostToDevice, f->stream));
   }
   AccArgs a{};
-  a.ent = f->ent;
-  a.off = f->off;
-  a.rbase = f->rbase;
+  a.ent = f->ent.as<const uint32_t>();
+  a.off = f->off.as<const uint32_t>();
+  a.rbase = f->rbase.as<const uint64_t>();
   a.dim1 = f->dim + 1;
   a.n_docs = f->n_docs;
   a.n_ranges = f->n_ranges;
   a.f16 = f->f16;
   a.val_scale = f->val_scale;
-  a.q_off = d_qoff;
-  a.comps = (const uint32_t*)f->scratch[1];
-  a.vals = (const float*)f->scratch[2];
+  a.q_off = f->q_off.as<const uint64_t>();
+  a.comps = f->q_comp.as<const uint32_t>();
+  a.vals = f->q_val.as<const float>();
   a.k = k;
-  a.cand = (uint64_t*)f->scratch[3];
+  a.cand = f->cand.as<uint64_t>();
   a.bits = bits;
   for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
     const uint32_t n = std::min(chunk, nq - q0);
@@ -631,16 +507,16 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
     const uint64_t tasks = (uint64_t)n * f->n_ranges;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(tasks, f->n_cu);
     hipLaunchKernelGGL(exact_accumulate_kernel, dim3(grid), dim3(kBS), 0, f->stream, a);
-    EX_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     ++f->last_launches;
     hipLaunchKernelGGL(exact_merge_kernel, dim3(n), dim3(kMergeBS), 0, f->stream, (const uint64_t*)a.cand, f->n_ranges,
-                       k, out_nn, q0, (float*)f->scratch[4], (uint64_t*)f->scratch[5], f->d_n);
-    EX_TRY(hipGetLastError());
+                       k, out_nn, q0, f->out_scores.as<float>(), f->out_ids.as<uint64_t>(), f->out_n.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
   }
-  EX_TRY(hipMemcpyAsync(out_scores, f->scratch[4], (uint64_t)nq * k * 4, hipMemcpyDeviceToHost, f->stream));
-  EX_TRY(hipMemcpyAsync(out_ids, f->scratch[5], (uint64_t)nq * k * 8, hipMemcpyDeviceToHost, f->stream));
-  EX_TRY(hipMemcpyAsync(out_n, f->d_n, (uint64_t)nq * 4, hipMemcpyDeviceToHost, f->stream));
-  EX_TRY(hipStreamSynchronize(f->stream));
+  HIP_TRY(hipMemcpyAsync(out_scores, f->out_scores.p, (uint64_t)nq * k * 4, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(out_ids, f->out_ids.p, (uint64_t)nq * k * 8, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(out_n, f->out_n.p, (uint64_t)nq * 4, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipStreamSynchronize(f->stream));
   return SGPU_OK;
 }
 
@@ -655,31 +531,11 @@ sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_
   }
   if (k == 0) return fail(SGPU_EINVAL, "k == 0");
   if (k > kMaxK) return fail(SGPU_ELIMIT, "k = %u exceeds the limit of %u", k, kMaxK);
-  ExactFile* f = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(idx->exact_mu);
-    if (replica >= idx->replicas.size())
-      return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
-    if (idx->exact.size() != idx->replicas.size()) idx->exact.resize(idx->replicas.size(), nullptr);
-    if (!idx->exact[replica]) {
-      ExactFile* nf = new (std::nothrow) ExactFile();
-      if (!nf) return fail(SGPU_ENOMEM, "out of host memory");
-      sgpu_status st;
-      try {
-        st = exact_file_build_on(idx->host, device_index_device(idx->replicas[replica]), nf);
-      } catch (const std::bad_alloc&) {
-        st = fail(SGPU_ENOMEM, "out of host memory");
-      }
-      if (st != SGPU_OK) {
-        const std::string msg = last_error();
-        exact_file_free(nf);
-        last_error() = msg;
-        return st;
-      }
-      idx->exact[replica] = nf;
-    }
-    f = idx->exact[replica];
-  }
+  ExactFile* f = nullptr;   // (the replica's exact file, built on its first exact call)
+  const sgpu_status fst = replica_state(
+      idx, idx->exact_mu, idx->exact, replica, [&](ExactFile* nf, int device) { return exact_file_build_on(idx->host, device, nf); },
+      exact_file_free, &f);
+  if (fst != SGPU_OK) return fst;
   const FilterDeviceView* fv = nullptr;
   if (filter) {   // (the filter's view on this replica holds its bitmap there)
     const sgpu_status st = filter_view(filter, replica, &fv);

@@ -21,13 +21,11 @@
 #include <new>
 #include <vector>
 
+#include "device_prims.hpp"
 #include "filter.hpp"
+#include "hip_util.hpp"
 
 namespace sgpu {
-
-// (device_index.hip)
-int device_index_device(const DeviceIndex* d);
-const DevView& device_index_view(const DeviceIndex* d);
 
 namespace {
 
@@ -61,16 +59,6 @@ __global__ __launch_bounds__(kBS) void filter_flag_kernel(const uint32_t* __rest
     if (lane < kTileWords && wi < n_words) flags[wi] = mine;
     if (lane == 0) tile_cnt[t] = cnt;
   }
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const uint32_t lane = __lane_id();
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 // One workgroup: base[t] = kept postings of the tiles before t, base[n] = all of them.
@@ -168,6 +156,19 @@ struct FilterView {
   uint64_t bytes = 0;
   float build_ms = 0;        // device time of the build (events around its copies and kernels)
   double build_wall_ms = 0;  // wall time of the build, allocations included
+};
+
+// The stream of a view's build and the two events around it: gone, the stream drained first, when the build returns.
+struct BuildStream {
+  hipStream_t s = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~BuildStream() {
+    if (!s) return;
+    (void)hipStreamSynchronize(s);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipStreamDestroy(s);
+  }
 };
 
 static void filter_view_free(FilterView* v) {
@@ -271,66 +272,51 @@ static sgpu_status view_build(const sgpu_filter* f, const DeviceIndex* d, uint64
       (st = dalloc((void**)&flags, n_words * 8, false)) != SGPU_OK || (st = dalloc((void**)&tiles, (n_tiles + 1) * 4, false)) != SGPU_OK ||
       (st = dalloc((void**)&word_base, n_words * 4, false)) != SGPU_OK)
     return st;
-  hipStream_t s = nullptr;
-  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return fail(SGPU_EDEVICE, "hipStreamCreate failed");
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto done = [&](sgpu_status r) {
-    (void)hipStreamSynchronize(s);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(s);
-    return r;
-  };
-#define FV_TRY(expr)                                                                                                  \
-  do {                                                                                                               \
-    hipError_t e_ = (expr);                                                                                          \
-    if (e_ != hipSuccess)                                                                                            \
-      return done(fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__));   \
-  } while (0)
-  FV_TRY(hipEventCreate(&e0));
-  FV_TRY(hipEventCreate(&e1));
+  BuildStream bs;
+  if (hipStreamCreateWithFlags(&bs.s, hipStreamNonBlocking) != hipSuccess) return fail(SGPU_EDEVICE, "hipStreamCreate failed");
+  HIP_TRY(hipEventCreate(&bs.e0));
+  HIP_TRY(hipEventCreate(&bs.e1));
+  const hipStream_t s = bs.s;
   int n_cu = 0;
-  FV_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, v->device));
+  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, v->device));
   const uint32_t waves_per_wg = kBS / 64;
   auto grid_for = [&](uint64_t units, uint64_t per_wg) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + per_wg - 1) / per_wg, 16ull * (uint64_t)std::max(n_cu, 1)));
   };
   (void)hipGetLastError();   // (judge these launches alone)
-  FV_TRY(hipEventRecord(e0, s));
-  FV_TRY(hipMemcpyAsync(bits, f->bits.data(), n_bits * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(bs.e0, s));
+  HIP_TRY(hipMemcpyAsync(bits, f->bits.data(), n_bits * 4, hipMemcpyHostToDevice, s));
   uint32_t total = 0;
   if (n_p) {
     hipLaunchKernelGGL(filter_flag_kernel, dim3(grid_for(n_tiles, waves_per_wg)), dim3(kBS), 0, s, base.post_doc, n_p, bits, n_words,
                        n_tiles, flags, tiles);
-    FV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, s, tiles, n_tiles, tiles);
-    FV_TRY(hipGetLastError());
-    FV_TRY(hipMemcpyAsync(&total, tiles + n_tiles, 4, hipMemcpyDeviceToHost, s));
-    FV_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&total, tiles + n_tiles, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   if ((st = dalloc((void**)&ref, (uint64_t)total * 8, true)) != SGPU_OK || (st = dalloc((void**)&doc, (uint64_t)total * 4, true)) != SGPU_OK)
-    return done(st);
+    return st;
   if (n_p) {
     hipLaunchKernelGGL(filter_scatter_kernel, dim3(grid_for(n_tiles, waves_per_wg)), dim3(kBS), 0, s, flags, n_words, n_tiles,
                        tiles, base.post_ref, base.post_doc, ref, doc, word_base);
-    FV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_blocks_kernel, dim3(grid_for(n_blocks + 1, kBS)), dim3(kBS), 0, s, base.block_post_start, n_blocks + 1,
                        flags, word_base, n_words, total, bps);
-    FV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   } else {
-    FV_TRY(hipMemsetAsync(bps, 0, (n_blocks + 1) * 4, s));
+    HIP_TRY(hipMemsetAsync(bps, 0, (n_blocks + 1) * 4, s));
   }
   if (base.knn && base.knn_total) {
-    if ((st = dalloc((void**)&knn, base.knn_total * 4, true)) != SGPU_OK) return done(st);
+    if ((st = dalloc((void**)&knn, base.knn_total * 4, true)) != SGPU_OK) return st;
     hipLaunchKernelGGL(filter_knn_kernel, dim3(grid_for(base.knn_total, kBS)), dim3(kBS), 0, s, base.knn, base.knn_total, bits,
                        base.n_docs, knn);
-    FV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
-  FV_TRY(hipEventRecord(e1, s));
-  FV_TRY(hipStreamSynchronize(s));
-  FV_TRY(hipEventElapsedTime(&v->build_ms, e0, e1));
-#undef FV_TRY
-  done(SGPU_OK);
+  HIP_TRY(hipEventRecord(bs.e1, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipEventElapsedTime(&v->build_ms, bs.e0, bs.e1));
   // the scratch goes; what stays is the view's
   for (void* p : {(void*)flags, (void*)tiles, (void*)word_base}) {
     (void)hipFree(p);

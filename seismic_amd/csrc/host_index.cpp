@@ -66,6 +66,11 @@ sgpu_status fail(sgpu_status st, const char* fmt, ...) {
   return st;
 }
 
+bool test_hooks_on() {
+  const char* t = std::getenv("SGPU_TEST_HOOKS");
+  return t && *t && *t != '0';
+}
+
 void HostIndex::fill_desc(sgpu_index_desc* d) const {
   std::memset(d, 0, sizeof *d);
   d->comp_width = comp_width;

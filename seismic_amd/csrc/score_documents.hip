@@ -12,10 +12,9 @@
 // dense f32 table over the vocabulary where dim + 1 floats fit kScoreDenseLds bytes, else an open-addressing hash table
 // {component, weight} at most half full - and rebuilds it only when its next tile belongs to another query. Every
 // candidate is scored by a 16-lane group: lane l loads elements [8 l, 8 l + 8) of each 128-element round with 16-byte
-// loads, kScoreDocs candidates per group in flight. The record forms are those pack_index.cpp writes:
-//   raw      [npad components (u16 / u32)][npad values (binary16 / u8 codes)], npad = len rounded up to 8
-//   sliced   (DotVByte) [ns x 16 B: 96 bits of first component + gaps | codes 0-3][ns x 4 B: codes 4-7], ns = npad / 8;
-//            bit 15 of the ref's length field: the document keeps the raw (u16, u8) form instead
+// loads, kScoreDocs candidates per group in flight. The record forms are those pack_index.cpp writes - raw, and sliced
+// for the documents of a DotVByte index that bit 15 of the ref's length field does not mark as raw -; record.hpp
+// describes them and decodes them, here as in the search kernels.
 //
 // sgpu_rerank_documents adds the SELECTION on the device: per query the k best DISTINCT candidates, score descending, id
 // ascending. score_documents_kernel is used as it is and leaves a launch's scores in the device scratch; what follows it
@@ -49,16 +48,13 @@
 #include <cstdlib>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
-#include "device_types.hpp"
-#include "host_index.hpp"
+#include "device_prims.hpp"
+#include "hip_util.hpp"
 
 namespace sgpu {
-
-// (device_index.hip)
-int device_index_device(const DeviceIndex* d);
-const DevView& device_index_view(const DeviceIndex* d);
 
 namespace {
 
@@ -68,7 +64,6 @@ constexpr uint32_t kScoreDenseLds = 128u << 10;  // the dense table is used wher
 constexpr uint32_t kScoreChunk = 1u << 20;       // candidates per launch (SGPU_SCORE_CHUNK overrides)
 constexpr uint32_t kHashEmpty = 0xffffffffu;
 constexpr uint32_t kNoQuery = 0xffffffffu;
-enum { SVT_F16 = 0, SVT_U8 = 1, SVT_DVB = 2 };
 
 struct ScoreArgs {
   const uint8_t* fwd;        // DevView::fwd (the document-major records lie at its start in both forward layouts)
@@ -84,77 +79,6 @@ struct ScoreArgs {
   uint32_t slot_bits;        // hash table: log2 of its slots
   float val_scale;
 };
-
-__device__ __forceinline__ float half_to_f32(uint32_t h) {   // exact binary16 -> binary32
-  const unsigned short b = (unsigned short)h;
-  _Float16 x;
-  __builtin_memcpy(&x, &b, 2);
-  return (float)x;
-}
-
-struct Slice {   // 8 consecutive elements of one document, as loaded
-  uint4 c0, c1;  // components (u16: c0; u32: c0, c1; sliced: the 96 gap bits in c0.xyz, codes 0-3 in c0.w)
-  uint4 v;       // 8 binary16 values, or 8 codes in v.x, v.y
-};
-
-template <int CW, int VT>
-__device__ __forceinline__ void load_slice(Slice& s, const uint8_t* rec, uint32_t len, bool raw, uint32_t sl) {
-  const uint32_t npad = (len + 7u) & ~7u;
-  if (VT == SVT_DVB && !raw) {
-    s.c0 = *(const uint4*)(rec + (size_t)sl * 16u);
-    s.v.x = s.c0.w;
-    s.v.y = *(const uint32_t*)(rec + (size_t)(npad >> 3) * 16u + (size_t)sl * 4u);
-    return;
-  }
-  s.c0 = *(const uint4*)(rec + (size_t)sl * 8u * CW);
-  if (CW == 4) s.c1 = *(const uint4*)(rec + (size_t)sl * 32u + 16u);
-  const uint8_t* pv = rec + (size_t)npad * CW;
-  if (VT == SVT_F16) {
-    s.v = *(const uint4*)(pv + (size_t)sl * 16u);
-  } else {
-    const uint2 t = *(const uint2*)(pv + (size_t)sl * 8u);
-    s.v.x = t.x;
-    s.v.y = t.y;
-  }
-}
-
-template <int CW, int VT>
-__device__ __forceinline__ void slice_components(const Slice& s, bool raw, uint32_t c[8]) {
-  if (VT == SVT_DVB && !raw) {
-    const uint32_t w0 = s.c0.x, w1 = s.c0.y, w2 = s.c0.z;
-    uint32_t run = w0 & 0xffffu;
-    c[0] = run;
-    run += (w0 >> 16) & 0xfffu;
-    c[1] = run;
-    run += ((w0 >> 28) | (w1 << 4)) & 0xfffu;
-    c[2] = run;
-    run += (w1 >> 8) & 0xfffu;
-    c[3] = run;
-    run += (w1 >> 20) & 0x7ffu;
-    c[4] = run;
-    run += ((w1 >> 31) | (w2 << 1)) & 0x7ffu;
-    c[5] = run;
-    run += (w2 >> 10) & 0x7ffu;
-    c[6] = run;
-    run += w2 >> 21;
-    c[7] = run;
-    return;
-  }
-  if (CW == 2) {
-    c[0] = s.c0.x & 0xffffu; c[1] = s.c0.x >> 16; c[2] = s.c0.y & 0xffffu; c[3] = s.c0.y >> 16;
-    c[4] = s.c0.z & 0xffffu; c[5] = s.c0.z >> 16; c[6] = s.c0.w & 0xffffu; c[7] = s.c0.w >> 16;
-  } else {
-    c[0] = s.c0.x; c[1] = s.c0.y; c[2] = s.c0.z; c[3] = s.c0.w;
-    c[4] = s.c1.x; c[5] = s.c1.y; c[6] = s.c1.z; c[7] = s.c1.w;
-  }
-}
-
-template <int VT>
-__device__ __forceinline__ float slice_value(const Slice& s, int i) {
-  const uint32_t v[4] = {s.v.x, s.v.y, s.v.z, s.v.w};
-  if (VT == SVT_F16) return half_to_f32((v[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-  return (float)((v[i >> 2] >> (8 * (i & 3))) & 0xffu);
-}
 
 // the query's weight of component c (0.0: the query does not carry it). Dense: tab[c], c <= dim. Hash: linear probing
 // from the component's slot; the table is at most half full, so a probe sequence always meets an empty slot.
@@ -175,6 +99,7 @@ __device__ __forceinline__ float weight_of(const uint8_t* smem, uint32_t c, uint
 
 template <int CW, int VT, bool DENSE>
 __global__ __launch_bounds__(1024) void score_documents_kernel(ScoreArgs a) {
+  using CT = typename std::conditional<CW == 2, uint16_t, uint32_t>::type;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const uint32_t ng = nt >> 4, g = tid >> 4, l = tid & 15u;
@@ -202,7 +127,7 @@ __global__ __launch_bounds__(1024) void score_documents_kernel(ScoreArgs a) {
       for (uint64_t j = b0 + tid; j < b1; j += nt) {
         const uint32_t c = a.q_comp[j];
         // fixed-u8 codes: value = code * val_scale, a power of two folded into the weight (exact), as the search kernels do
-        const float w = VT == SVT_F16 ? a.q_val[j] : __fmul_rn(a.q_val[j], a.val_scale);
+        const float w = Vt<VT>::half ? a.q_val[j] : __fmul_rn(a.q_val[j], a.val_scale);
         if (DENSE) {
           ((float*)smem)[c] = w;
         } else {
@@ -226,28 +151,32 @@ __global__ __launch_bounds__(1024) void score_documents_kernel(ScoreArgs a) {
       for (uint32_t u = 0; u < kScoreDocs; ++u) {
         idx[u] = base + u * ng + g;
         const uint64_t ref = idx[u] < tile.z ? a.doc_ref[a.cand[tile.y + idx[u]]] : 0ull;
-        const uint32_t lf = (uint32_t)ref & 0xffffu;
-        len[u] = VT == SVT_DVB ? (lf & 0x7fffu) : lf;
-        raw[u] = VT == SVT_DVB && (lf & 0x8000u) != 0u;
+        len[u] = (uint32_t)ref & LenMask<VT>::v;
+        raw[u] = Vt<VT>::sliced && ((uint32_t)ref & kRawBit) != 0u;
         rec[u] = a.fwd + (size_t)(ref >> 16) * 16u;
         acc[u] = 0.0f;
         max_len = max(max_len, len[u]);
       }
       for (uint32_t e0 = l * 8u; e0 < max_len; e0 += 128u) {
-        Slice s[kScoreDocs];
+        DocChunk<CT, VT> d[kScoreDocs];
 #pragma unroll
         for (uint32_t u = 0; u < kScoreDocs; ++u)
-          if (e0 < len[u]) load_slice<CW, VT>(s[u], rec[u], len[u], raw[u], e0 >> 3);
+          if (e0 < len[u]) load_pass<CT, VT>(d[u], rec[u], len[u], raw[u], e0);
 #pragma unroll
         for (uint32_t u = 0; u < kScoreDocs; ++u)
           if (e0 < len[u]) {
             uint32_t c[8];
-            slice_components<CW, VT>(s[u], raw[u], c);
+            if (Vt<VT>::sliced && raw[u]) {
+              raw_pass_components<CT, VT>(d[u], c);
+            } else {
+              slice_components<CT, VT>(d[u], c);
+            }
+            place_values<CT, VT>(d[u], raw[u]);
             float w[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) w[i] = weight_of<DENSE>(smem, c[i], a.slot_bits);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) acc[u] = __fadd_rn(acc[u], __fmul_rn(w[i], slice_value<VT>(s[u], i)));
+            for (int i = 0; i < 8; ++i) acc[u] = __fadd_rn(acc[u], __fmul_rn(w[i], slice_value<VT>(d[u].v, i)));
           }
       }
 #pragma unroll
@@ -265,13 +194,13 @@ __global__ __launch_bounds__(1024) void score_documents_kernel(ScoreArgs a) {
 
 using ScoreKernel = void (*)(ScoreArgs);
 ScoreKernel score_kernel(uint32_t cw, uint32_t vt, bool dense) {
-  if (vt == SGPU_VAL_DOTVBYTE) return dense ? score_documents_kernel<2, SVT_DVB, true> : score_documents_kernel<2, SVT_DVB, false>;
+  if (vt == SGPU_VAL_DOTVBYTE) return dense ? score_documents_kernel<2, VT_DVB, true> : score_documents_kernel<2, VT_DVB, false>;
   if (vt == SGPU_VAL_FIXEDU8) {
-    if (cw == 2) return dense ? score_documents_kernel<2, SVT_U8, true> : score_documents_kernel<2, SVT_U8, false>;
-    return dense ? score_documents_kernel<4, SVT_U8, true> : score_documents_kernel<4, SVT_U8, false>;
+    if (cw == 2) return dense ? score_documents_kernel<2, VT_U8, true> : score_documents_kernel<2, VT_U8, false>;
+    return dense ? score_documents_kernel<4, VT_U8, true> : score_documents_kernel<4, VT_U8, false>;
   }
-  if (cw == 2) return dense ? score_documents_kernel<2, SVT_F16, true> : score_documents_kernel<2, SVT_F16, false>;
-  return dense ? score_documents_kernel<4, SVT_F16, true> : score_documents_kernel<4, SVT_F16, false>;
+  if (cw == 2) return dense ? score_documents_kernel<2, VT_F16, true> : score_documents_kernel<2, VT_F16, false>;
+  return dense ? score_documents_kernel<4, VT_F16, true> : score_documents_kernel<4, VT_F16, false>;
 }
 
 
@@ -308,14 +237,9 @@ struct SelArgs {
 };
 
 __device__ __forceinline__ uint64_t sel_key(float score, uint32_t id) {
-  const uint32_t b = __float_as_uint(score);
-  const uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((uint64_t)o << 32) | (uint64_t)(~id);
+  return ((uint64_t)ordered_u32(score) << 32) | (uint64_t)(~id);
 }
-__device__ __forceinline__ float sel_key_score(uint64_t key) {
-  const uint32_t o = (uint32_t)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+__device__ __forceinline__ float sel_key_score(uint64_t key) { return ordered_u32_inv((uint32_t)(key >> 32)); }
 
 __global__ __launch_bounds__(kSelBlock) void rerank_select_kernel(SelArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -343,19 +267,9 @@ __global__ __launch_bounds__(kSelBlock) void rerank_select_kernel(SelArgs a) {
       key[i] = v;
     }
     __syncthreads();
-    for (uint32_t size = 2; size <= cap; size <<= 1)
-      for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-        for (uint32_t p = lt; p < (cap >> 1); p += team) {
-          const uint32_t i = 2u * p - (p & (stride - 1u)), j = i + stride;
-          const uint64_t x = key[i], y = key[j];
-          const bool desc = (i & size) == 0u;
-          if ((x < y) == desc && x != y) {
-            key[i] = y;
-            key[j] = x;
-          }
-        }
-        __syncthreads();
-      }
+    // (its barriers are workgroup-uniform because every team of a launch sorts the same cap keys, a team without a task
+    // its padding: keep cap a property of the launch, never of the task)
+    bitonic_sort_lds<true>(key, cap, lt, team);
     // distinct keys that are no padding, counted per thread over its run of the sorted keys ...
     uint32_t cnt = 0;
     const uint32_t e0 = lt * per;
@@ -365,11 +279,7 @@ __global__ __launch_bounds__(kSelBlock) void rerank_select_kernel(SelArgs a) {
         cnt += (v != 0 && (e == 0 || v != key[e - 1])) ? 1u : 0u;
       }
     // ... and their exclusive prefix sum over the team: within a wave by shuffles, across its waves through LDS
-    uint32_t incl = cnt;
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-      const uint32_t u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
+    const uint32_t incl = wave_incl_scan(cnt);
     if (lane == 63u) wave_total[w] = incl;
     __syncthreads();
     uint32_t before = incl - cnt, total = 0;
@@ -408,13 +318,6 @@ __global__ __launch_bounds__(kSelBlock) void rerank_select_kernel(SelArgs a) {
 }
 }  // namespace
 
-#define SC_TRY(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess)                                                                                     \
-      return fail(SGPU_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
 // Per replica: the score calls' stream, their recycled scratch and what the last call measured.
 struct ScoreState {
   int device = -1;
@@ -422,13 +325,14 @@ struct ScoreState {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   std::mutex mu;   // one score or rerank call at a time on this replica
-  // q_off, comps, vals, tiles, candidate ids, scores; rerank: tasks, slots, carry slots, row scores, row ids, row counts
-  void* scratch[12] = {};
-  uint64_t scratch_bytes[12] = {};
-  std::vector<uint4> tiles;     // host staging of a launch
-  std::vector<uint32_t> ids;
+  DeviceBuffer q_off, q_comp, q_val;   // the call's queries
+  DeviceBuffer tiles, cand, scores;    // a launch's tiles, candidate ids and scores
+  // rerank: a launch's selection tasks and k-key slots, the two carry slots, the call's rows (scores, ids, counts)
+  DeviceBuffer sel_tasks, slots, carry, row_scores, row_ids, row_n;
+  std::vector<uint4> h_tiles;   // host staging of a launch
+  std::vector<uint32_t> h_ids;
   std::vector<std::vector<SelTask>> sel_rounds;   // [round * tiers + tier]
-  std::vector<SelTask> sel_tasks;
+  std::vector<SelTask> h_sel_tasks;
   double last_select_ms = 0;    // rerank: device time of the selection kernels, merge rounds run
   uint32_t last_merge_rounds = 0;
   double last_kernel_ms = 0;    // device time of the last call's kernels, its launches and its lookup form (sgpu_debug_score_stats)
@@ -439,7 +343,9 @@ void score_state_free(ScoreState* s) {
   if (!s) return;
   if (s->device >= 0) (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
-  for (void* p : s->scratch) if (p) (void)hipFree(p);
+  for (DeviceBuffer* b : {&s->q_off, &s->q_comp, &s->q_val, &s->tiles, &s->cand, &s->scores, &s->sel_tasks, &s->slots, &s->carry,
+                          &s->row_scores, &s->row_ids, &s->row_n})
+    b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   if (s->ev2) (void)hipEventDestroy(s->ev2);
@@ -449,39 +355,18 @@ void score_state_free(ScoreState* s) {
 
 static sgpu_status score_state_init(ScoreState* s, int device) {
   s->device = device;
-  SC_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   int n_cu = 0;
-  SC_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
   s->n_cu = (uint32_t)std::max(n_cu, 1);
-  SC_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  SC_TRY(hipEventCreate(&s->ev0));
-  SC_TRY(hipEventCreate(&s->ev1));
-  SC_TRY(hipEventCreate(&s->ev2));
+  HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreate(&s->ev0));
+  HIP_TRY(hipEventCreate(&s->ev1));
+  HIP_TRY(hipEventCreate(&s->ev2));
   return SGPU_OK;
 }
 
-static sgpu_status score_scratch(ScoreState* s, int i, uint64_t bytes) {
-  if (s->scratch_bytes[i] >= bytes && s->scratch[i]) return SGPU_OK;
-  if (s->scratch[i]) {
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipFree(s->scratch[i]);
-    s->scratch[i] = nullptr;
-    s->scratch_bytes[i] = 0;
-  }
-  bytes = std::max<uint64_t>(bytes, 16);
-  if (hipMalloc(&s->scratch[i], bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    s->scratch[i] = nullptr;
-    return fail(SGPU_ENOMEM, "out of device memory scoring documents (%llu bytes)", (unsigned long long)bytes);
-  }
-  s->scratch_bytes[i] = bytes;
-  return SGPU_OK;
-}
-
-static bool score_hooks_on() {
-  const char* t = std::getenv("SGPU_TEST_HOOKS");
-  return t && *t && *t != '0';
-}
+static sgpu_status score_reserve(ScoreState* s, DeviceBuffer& b, uint64_t bytes) { return b.reserve(s->stream, bytes, "scoring documents"); }
 
 // A rerank call: what the selection needs beyond a score call (null for sgpu_score_documents).
 struct RerankCall {
@@ -497,7 +382,7 @@ struct RerankCall {
 
 static void rerank_setup(RerankCall* rr) {
   uint32_t c = kRerankChunk;
-  if (score_hooks_on()) {
+  if (test_hooks_on()) {
     if (const char* v = std::getenv("SGPU_RERANK_CHUNK"))
       if (*v) {
         const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(2, std::strtoull(v, nullptr, 10)), kRerankChunk);
@@ -575,10 +460,77 @@ static uint32_t rerank_plan(ScoreState* s, RerankCall* rr, const uint64_t* cand_
   return next_slot;
 }
 
+// The call's rows on the device, zeroed (a selection task writes the slots it fills and the row's count), and what the
+// selection launches of the call have in common.
+static sgpu_status rerank_rows_begin(ScoreState* s, const RerankCall* rr, uint32_t nq, SelArgs* sel) {
+  const uint64_t cells = (uint64_t)nq * rr->k;
+  sgpu_status st;
+  if ((st = score_reserve(s, s->carry, 2ull * rr->k * 8)) != SGPU_OK || (st = score_reserve(s, s->row_scores, cells * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->row_ids, cells * 8)) != SGPU_OK || (st = score_reserve(s, s->row_n, (uint64_t)nq * 4)) != SGPU_OK)
+    return st;
+  HIP_TRY(hipMemsetAsync(s->row_scores.p, 0, cells * 4, s->stream));
+  HIP_TRY(hipMemsetAsync(s->row_ids.p, 0, cells * 8, s->stream));
+  HIP_TRY(hipMemsetAsync(s->row_n.p, 0, (uint64_t)nq * 4, s->stream));
+  sel->carry = s->carry.as<uint64_t>();
+  sel->row_scores = s->row_scores.as<float>();
+  sel->row_ids = s->row_ids.as<uint64_t>();
+  sel->row_n = s->row_n.as<uint32_t>();
+  sel->k = rr->k;
+  HIP_TRY(hipFuncSetAttribute((const void*)rerank_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kRerankChunk * 8u)));
+  return SGPU_OK;
+}
+
+// The selection over one launch's scores - candidates [first, last) of the call, the queries from q_first on -: one
+// launch per round and tier, in the stream's order behind the score kernel.
+static sgpu_status rerank_select(ScoreState* s, RerankCall* rr, SelArgs sel, const uint64_t* cand_off, uint32_t nq, uint32_t q_first,
+                                 uint64_t first, uint64_t last) {
+  const uint32_t n_slots = rerank_plan(s, rr, cand_off, nq, q_first, first, last);
+  s->h_sel_tasks.clear();
+  for (const auto& v : s->sel_rounds) s->h_sel_tasks.insert(s->h_sel_tasks.end(), v.begin(), v.end());
+  sgpu_status st;
+  if ((st = score_reserve(s, s->sel_tasks, s->h_sel_tasks.size() * sizeof(SelTask))) != SGPU_OK ||
+      (st = score_reserve(s, s->slots, (uint64_t)n_slots * rr->k * 8)) != SGPU_OK)
+    return st;
+  HIP_TRY(hipMemcpyAsync(s->sel_tasks.p, s->h_sel_tasks.data(), s->h_sel_tasks.size() * sizeof(SelTask), hipMemcpyHostToDevice,
+                         s->stream));
+  sel.scores = s->scores.as<const float>();
+  sel.cand = s->cand.as<const uint32_t>();
+  sel.slots = s->slots.as<uint64_t>();
+  size_t at = 0;
+  for (size_t i = 0; i < s->sel_rounds.size(); ++i) {
+    const size_t n = s->sel_rounds[i].size();
+    if (!n) continue;
+    const SelTier& tier = rr->tiers[i % rr->n_tiers];
+    const uint32_t teams = kSelBlock / tier.team;
+    sel.tasks = s->sel_tasks.as<const SelTask>() + at;
+    sel.n_tasks = (uint32_t)n;
+    sel.cap = tier.cap;
+    sel.team = tier.team;
+    const uint32_t sel_grid = (uint32_t)std::min<uint64_t>((n + teams - 1) / teams, (uint64_t)s->n_cu * (2048u / kSelBlock));
+    hipLaunchKernelGGL(rerank_select_kernel, dim3(sel_grid), dim3(kSelBlock), teams * tier.cap * 8u, s->stream, sel);
+    HIP_TRY(hipGetLastError());
+    at += n;
+  }
+  HIP_TRY(hipEventRecord(s->ev2, s->stream));
+  s->last_merge_rounds += (uint32_t)(s->sel_rounds.size() / rr->n_tiers) - 1u;
+  return SGPU_OK;
+}
+
+static sgpu_status rerank_rows_end(ScoreState* s, const RerankCall* rr, uint32_t nq) {
+  const uint64_t cells = (uint64_t)nq * rr->k;
+  HIP_TRY(hipMemcpyAsync(rr->out_scores, s->row_scores.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(rr->out_doc_ids, s->row_ids.p, cells * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(rr->out_n, s->row_n.p, (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SGPU_OK;
+}
+
+// A score call (rr null: every candidate's score to out_scores) or a rerank call (rr: the selection follows each launch
+// on the stream, and the call's rows come back at the end).
 static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
                              const float* vals, uint32_t nq, uint32_t max_nnz, const uint64_t* cand_off, const uint64_t* cand_ids,
                              float* out_scores, RerankCall* rr = nullptr) {
-  SC_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->device));
   s->last_kernel_ms = 0;
   s->last_launches = 0;
   s->last_select_ms = 0;
@@ -587,7 +539,7 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
   // (test hook SGPU_SCORE_LOOKUP: 1 = dense where it fits, 2 = hash)
   const uint64_t dense_bytes = ((h.dim + 1) * 4 + 15) & ~15ull;
   bool dense = dense_bytes <= kScoreDenseLds;
-  if (score_hooks_on()) {
+  if (test_hooks_on()) {
     const char* v = std::getenv("SGPU_SCORE_LOOKUP");
     if (v && *v == '2') dense = false;
   }
@@ -596,9 +548,9 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
   const uint32_t lds = dense ? (uint32_t)dense_bytes : (8u << slot_bits);
   const uint32_t block = lds > (40u << 10) ? 1024u : (lds > (20u << 10) ? 512u : 256u);
   ScoreKernel kern = score_kernel(h.comp_width, h.value_type, dense);
-  SC_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
-  SC_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)block, lds));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)block, lds));
   if (per_cu < 1) return fail(SGPU_ELIMIT, "the score kernel does not fit on a CU (%u bytes of LDS)", lds);
   per_cu = std::min(per_cu, (int)(2048u / block));
 
@@ -610,20 +562,20 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
 
   const uint64_t qnnz = q_off[nq];
   sgpu_status st;
-  if ((st = score_scratch(s, 0, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = score_scratch(s, 1, qnnz * 4)) != SGPU_OK ||
-      (st = score_scratch(s, 2, qnnz * 4)) != SGPU_OK)
+  if ((st = score_reserve(s, s->q_off, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = score_reserve(s, s->q_comp, qnnz * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->q_val, qnnz * 4)) != SGPU_OK)
     return st;
-  SC_TRY(hipMemcpyAsync(s->scratch[0], q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->q_off.p, q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, s->stream));
   if (qnnz) {
-    SC_TRY(hipMemcpyAsync(s->scratch[1], comps, qnnz * 4, hipMemcpyHostToDevice, s->stream));
-    SC_TRY(hipMemcpyAsync(s->scratch[2], vals, qnnz * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->q_comp.p, comps, qnnz * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->q_val.p, vals, qnnz * 4, hipMemcpyHostToDevice, s->stream));
   }
   ScoreArgs a{};
   a.fwd = view.fwd;
   a.doc_ref = view.doc_ref;
-  a.q_off = (const uint64_t*)s->scratch[0];
-  a.q_comp = (const uint32_t*)s->scratch[1];
-  a.q_val = (const float*)s->scratch[2];
+  a.q_off = s->q_off.as<const uint64_t>();
+  a.q_comp = s->q_comp.as<const uint32_t>();
+  a.q_val = s->q_val.as<const float>();
   a.dim = (uint32_t)h.dim;
   a.slot_bits = slot_bits;
   a.val_scale = h.val_scale;
@@ -632,128 +584,61 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
   s->last_lds = lds;
 
   SelArgs sel{};
-  if (rr) {   // the call's rows on the device, zeroed: a selection task writes the slots it fills and the row's count
-    const uint64_t cells = (uint64_t)nq * rr->k;
-    if ((st = score_scratch(s, 8, 2ull * rr->k * 8)) != SGPU_OK || (st = score_scratch(s, 9, cells * 4)) != SGPU_OK ||
-        (st = score_scratch(s, 10, cells * 8)) != SGPU_OK || (st = score_scratch(s, 11, (uint64_t)nq * 4)) != SGPU_OK)
-      return st;
-    SC_TRY(hipMemsetAsync(s->scratch[9], 0, cells * 4, s->stream));
-    SC_TRY(hipMemsetAsync(s->scratch[10], 0, cells * 8, s->stream));
-    SC_TRY(hipMemsetAsync(s->scratch[11], 0, (uint64_t)nq * 4, s->stream));
-    sel.carry = (uint64_t*)s->scratch[8];
-    sel.row_scores = (float*)s->scratch[9];
-    sel.row_ids = (uint64_t*)s->scratch[10];
-    sel.row_n = (uint32_t*)s->scratch[11];
-    sel.k = rr->k;
-    SC_TRY(hipFuncSetAttribute((const void*)rerank_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(kRerankChunk * 8u)));
-  }
+  if (rr && (st = rerank_rows_begin(s, rr, nq, &sel)) != SGPU_OK) return st;
 
   // launches: consecutive tiles (a query's candidates in runs of at most tile_max) while they fit the budget
   uint32_t q = 0;
   uint64_t pos = 0;   // next candidate of the call
   const uint64_t total = cand_off[nq];
   while (pos < total) {
-    s->tiles.clear();
-    s->ids.clear();
+    s->h_tiles.clear();
+    s->h_ids.clear();
     const uint64_t first = pos;
     while (pos < total && pos - first < budget) {
       while (cand_off[q + 1] <= pos) ++q;
       const uint32_t n = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(tile_max, cand_off[q + 1] - pos), budget - (pos - first));
-      s->tiles.push_back(make_uint4(q, (uint32_t)(pos - first), n, 0u));
+      s->h_tiles.push_back(make_uint4(q, (uint32_t)(pos - first), n, 0u));
       pos += n;
     }
     const uint64_t n_cand = pos - first;
-    const uint32_t q_first = s->tiles.front().x;
-    s->ids.resize(n_cand);
-    for (uint64_t i = 0; i < n_cand; ++i) s->ids[i] = (uint32_t)cand_ids[first + i];
-    if ((st = score_scratch(s, 3, s->tiles.size() * sizeof(uint4))) != SGPU_OK || (st = score_scratch(s, 4, n_cand * 4)) != SGPU_OK ||
-        (st = score_scratch(s, 5, n_cand * 4)) != SGPU_OK)
+    s->h_ids.resize(n_cand);
+    for (uint64_t i = 0; i < n_cand; ++i) s->h_ids[i] = (uint32_t)cand_ids[first + i];
+    if ((st = score_reserve(s, s->tiles, s->h_tiles.size() * sizeof(uint4))) != SGPU_OK ||
+        (st = score_reserve(s, s->cand, n_cand * 4)) != SGPU_OK || (st = score_reserve(s, s->scores, n_cand * 4)) != SGPU_OK)
       return st;
-    SC_TRY(hipMemcpyAsync(s->scratch[3], s->tiles.data(), s->tiles.size() * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
-    SC_TRY(hipMemcpyAsync(s->scratch[4], s->ids.data(), n_cand * 4, hipMemcpyHostToDevice, s->stream));
-    a.tiles = (const uint4*)s->scratch[3];
-    a.cand = (const uint32_t*)s->scratch[4];
-    a.out = (float*)s->scratch[5];
-    a.n_tiles = (uint32_t)s->tiles.size();
+    HIP_TRY(hipMemcpyAsync(s->tiles.p, s->h_tiles.data(), s->h_tiles.size() * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->cand.p, s->h_ids.data(), n_cand * 4, hipMemcpyHostToDevice, s->stream));
+    a.tiles = s->tiles.as<const uint4>();
+    a.cand = s->cand.as<const uint32_t>();
+    a.out = s->scores.as<float>();
+    a.n_tiles = (uint32_t)s->h_tiles.size();
     const uint32_t grid = (uint32_t)std::min<uint64_t>(a.n_tiles, (uint64_t)s->n_cu * (uint32_t)per_cu);
     s->last_grid = grid;
-    SC_TRY(hipEventRecord(s->ev0, s->stream));
+    HIP_TRY(hipEventRecord(s->ev0, s->stream));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s->stream, a);
-    SC_TRY(hipGetLastError());
-    SC_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
     if (!rr) {
-      SC_TRY(hipMemcpyAsync(out_scores + first, s->scratch[5], n_cand * 4, hipMemcpyDeviceToHost, s->stream));
-    } else {   // the selection over this launch's scores: one launch per round and tier, in the stream's order
-      const uint32_t n_slots = rerank_plan(s, rr, cand_off, nq, q_first, first, pos);
-      s->sel_tasks.clear();
-      for (const auto& v : s->sel_rounds) s->sel_tasks.insert(s->sel_tasks.end(), v.begin(), v.end());
-      if ((st = score_scratch(s, 6, s->sel_tasks.size() * sizeof(SelTask))) != SGPU_OK ||
-          (st = score_scratch(s, 7, (uint64_t)n_slots * rr->k * 8)) != SGPU_OK)
-        return st;
-      SC_TRY(hipMemcpyAsync(s->scratch[6], s->sel_tasks.data(), s->sel_tasks.size() * sizeof(SelTask), hipMemcpyHostToDevice,
-                            s->stream));
-      sel.scores = (const float*)s->scratch[5];
-      sel.cand = (const uint32_t*)s->scratch[4];
-      sel.slots = (uint64_t*)s->scratch[7];
-      size_t at = 0;
-      for (size_t i = 0; i < s->sel_rounds.size(); ++i) {
-        const size_t n = s->sel_rounds[i].size();
-        if (!n) continue;
-        const SelTier& tier = rr->tiers[i % rr->n_tiers];
-        const uint32_t teams = kSelBlock / tier.team;
-        sel.tasks = (const SelTask*)s->scratch[6] + at;
-        sel.n_tasks = (uint32_t)n;
-        sel.cap = tier.cap;
-        sel.team = tier.team;
-        const uint32_t sel_grid = (uint32_t)std::min<uint64_t>((n + teams - 1) / teams, (uint64_t)s->n_cu * (2048u / kSelBlock));
-        hipLaunchKernelGGL(rerank_select_kernel, dim3(sel_grid), dim3(kSelBlock), teams * tier.cap * 8u, s->stream, sel);
-        SC_TRY(hipGetLastError());
-        at += n;
-      }
-      SC_TRY(hipEventRecord(s->ev2, s->stream));
-      s->last_merge_rounds += (uint32_t)(s->sel_rounds.size() / rr->n_tiers) - 1u;
+      HIP_TRY(hipMemcpyAsync(out_scores + first, s->scores.p, n_cand * 4, hipMemcpyDeviceToHost, s->stream));
+    } else if ((st = rerank_select(s, rr, sel, cand_off, nq, s->h_tiles.front().x, first, pos)) != SGPU_OK) {
+      return st;
     }
-    SC_TRY(hipStreamSynchronize(s->stream));   // (the staging vectors and the scratch are the next launch's)
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (the staging vectors and the scratch are the next launch's)
     float ms = 0.0f;
-    SC_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->last_kernel_ms += ms;
     s->last_launches += 1;
     if (rr) {
-      SC_TRY(hipEventElapsedTime(&ms, s->ev1, s->ev2));
+      HIP_TRY(hipEventElapsedTime(&ms, s->ev1, s->ev2));
       s->last_select_ms += ms;
     }
   }
-  if (rr) {
-    const uint64_t cells = (uint64_t)nq * rr->k;
-    SC_TRY(hipMemcpyAsync(rr->out_scores, s->scratch[9], cells * 4, hipMemcpyDeviceToHost, s->stream));
-    SC_TRY(hipMemcpyAsync(rr->out_doc_ids, s->scratch[10], cells * 8, hipMemcpyDeviceToHost, s->stream));
-    SC_TRY(hipMemcpyAsync(rr->out_n, s->scratch[11], (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
-    SC_TRY(hipStreamSynchronize(s->stream));
-  }
-  return SGPU_OK;
+  return rr ? rerank_rows_end(s, rr, nq) : SGPU_OK;
 }
 
-// The replica's score state, made on its first score or rerank call (SGPU_EDEVICE: not uploaded / no such replica).
+// The replica's score state, made on its first score or rerank call.
 static sgpu_status score_state_of(sgpu_index* idx, uint32_t replica, ScoreState** out) {
-  std::lock_guard<std::mutex> lk(idx->score_mu);
-  if (replica >= idx->replicas.size())
-    return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
-  if (idx->score.size() != idx->replicas.size()) idx->score.resize(idx->replicas.size(), nullptr);
-  if (!idx->score[replica]) {
-    ScoreState* ns = new (std::nothrow) ScoreState();
-    if (!ns) return fail(SGPU_ENOMEM, "out of host memory");
-    const sgpu_status st = score_state_init(ns, device_index_device(idx->replicas[replica]));
-    if (st != SGPU_OK) {
-      const std::string msg = last_error();
-      score_state_free(ns);
-      last_error() = msg;
-      return st;
-    }
-    idx->score[replica] = ns;
-  }
-  *out = idx->score[replica];
-  return SGPU_OK;
+  return replica_state(idx, idx->score_mu, idx->score, replica, score_state_init, score_state_free, out);
 }
 
 sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,

@@ -67,10 +67,10 @@
 #include <cstdio>
 
 #include "device_types.hpp"
+#include "record.hpp"
 
 namespace sgpu {
 
-#define SGPU_DEV __device__ __forceinline__
 #ifndef SGPU_REPLAY_PRIO
 #define SGPU_REPLAY_PRIO 2
 #endif
@@ -101,13 +101,6 @@ SGPU_DEV float mul_f32_f16(float q, uint32_t packed, int hi) {
   else
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(q), "v"(packed), "s"(0x80000000u));
   return r;
-}
-
-SGPU_DEV float half_bits_to_float(uint32_t h) {   // exact binary16 -> binary32 (v_cvt_f32_f16)
-  const unsigned short b = (unsigned short)h;
-  _Float16 x;
-  __builtin_memcpy(&x, &b, 2);
-  return (float)x;
 }
 
 SGPU_DEV uint32_t lane_id() { return __lane_id(); }
@@ -771,131 +764,10 @@ SGPU_DEV void visited_mark(uint32_t* bitmap, uint32_t doc) {
 // Non-matching components resolve to the weight 0.0 (slot qn of q_val) and are
 // added as +-0.0, which leaves an accumulator that started at +0.0 bit-identical
 // to skipping them (x + (+-0) == x, and the accumulator can never be -0.0).
-// VT: how the record stores values - VT_F16 (binary16, 2 bytes) or VT_U8 (fixed-u8 codes, 1 byte;
-// value = code * val_scale with val_scale a power of two, folded into the weights: q_sc = q * val_scale
-// is exact, and fl(q_sc * code) == fl(q * (code * val_scale)), the product the oracle computes).
-// VT_DVB: the forward index of a DotVByte index (reference src/pylib/dotvbyte.rs:15-22): fixed-u8 codes as VT_U8 plus a
-// COMPRESSED component stream. The reference's codec (vectorium's DotVByte, a variable-byte gap stream - not in the
-// tree: parity unpinned) is lossless, so results are those of the fixed-u8 index; what is restated here is its role
-// in a GPU-shaped form: per 8-element slice THREE dwords instead of four -
-//     bits [0,16) the slice's first component, absolute
-//     bits [16,28) [28,40) [40,52)            the gaps of elements 1, 2, 3 to their predecessors (12 bits each)
-//     bits [52,63) [63,74) [74,85) [85,96)    the gaps of elements 4 .. 7 (11 bits each)
-// decoded by the lane that owns the slice with nine bit-field operations and a running sum of seven additions; no
-// lane needs another lane's data (the r04 first form - eight 12-bit gaps chained through the whole document - needed
-// a sum of the slice, a four-step DPP scan over the document's 16 lanes and a broadcast on top: +14.5 % per launch
-// against the fixed-u8 index; this form: see DESIGN.md section 5). With the dense lookup table the running sum starts
-// at the table's LDS address, so the sums ARE the addresses of the bytes to read (Lds::idx0).
-// Record (r05): [ns x 16 B: the slice's 12 bytes | codes of its elements 0-3][ns x 4 B: codes of elements 4-7], ns = ceil(len / 8); padding
-// elements have gap 0 and code 0 (they repeat the last component with value 0: +-0.0 added, exact). A
-// document with a gap that does not fit its field keeps the VT_U8 record form; bit 15 of the ref's length
-// field says which (documents of a DotVByte index have < 32768 components, checked at conversion).
-enum { VT_F16 = 0, VT_U8 = 1, VT_DVB = 2 };
-template <int VT> struct Vt {
-  static constexpr bool sliced = VT == VT_DVB;   // compressed component stream, raw fallback per document
-  static constexpr bool half = VT == VT_F16;     // binary16 values (else fixed-u8 codes)
-  static constexpr int raw = VT == VT_DVB ? VT_U8 : VT;   // the record form of a raw document
-  static constexpr uint32_t vbytes = half ? 16u : 8u;            // value bytes per slice
-};
-template <int VT> struct LenMask { static constexpr uint32_t v = Vt<VT>::sliced ? 0x7fffu : 0xffffu; };
-constexpr uint32_t kRawBit = 0x8000u;   // VT_DVB refs: the record is in the raw (VT_U8) form
-template <typename CT, int VT>
-struct DocChunk {   // 8 consecutive elements of one document, as loaded
-  uint4 c0, c1, v;   // v: 8 binary16 values (16 bytes), or 8 codes in v.x, v.y; sliced (VT_DVB): the gaps in c0.x, c0.y, c0.z
-};
+// How a record stores its elements (VT_F16, VT_U8, VT_DVB) and how a slice of 8 is loaded and unpacked: record.hpp.
 
-template <int VT>
-SGPU_DEV void load_values(uint4& v, const uint8_t* p) {
-  if (Vt<VT>::half) {
-    v = *(const uint4*)p;
-  } else {
-    const uint2 t = *(const uint2*)p;
-    v.x = t.x;
-    v.y = t.y;
-  }
-}
-
-// where slice `sl` (elements [8 sl, 8 sl + 8)) of a record lies: components (or gaps) and values
-template <typename CT, int VT>
-SGPU_DEV void slice_ptrs(const uint8_t* rec, uint32_t len, uint32_t sl, const uint8_t*& pc, const uint8_t*& pv) {
-  if (VT == VT_DVB) {
-    // r05: [ns x 16 B: w0 w1 w2 | codes 0-3][ns x 4 B: codes 4-7] - the slice's gaps AND its first four codes in ONE
-    // aligned 16-byte load, the other four codes in a dword (until r04: 12-byte slices, i.e. a 16-byte load at 4-byte
-    // alignment per lane: ~4 % of a launch, profiles/r04_dvb_layouts.txt). pv is read as 8 bytes like a raw record's
-    // codes (same load instruction for both record forms): the upper dword is the next slice's, ignored.
-    const uint32_t ns = (len + 7u) >> 3;
-    pc = rec + (size_t)sl * 16u;
-    pv = rec + (size_t)ns * 16u + (size_t)sl * 4u;
-  } else if (Vt<VT>::sliced) {
-    const uint32_t ns = (len + 7u) >> 3;
-    pc = rec + (size_t)sl * 12u;
-    pv = rec + (size_t)((ns * 12u + (Vt<VT>::vbytes - 1u)) & ~(Vt<VT>::vbytes - 1u)) + (size_t)sl * Vt<VT>::vbytes;
-  } else {
-    const uint32_t npad = (len + 7u) & ~7u;
-    pc = rec + (size_t)sl * 8u * sizeof(CT);
-    pv = rec + (size_t)npad * sizeof(CT) + (size_t)sl * Vt<VT>::vbytes;
-  }
-}
-
-template <typename CT, int VT>
-SGPU_DEV void load_slice(DocChunk<CT, VT>& d, const uint8_t* pc, const uint8_t* pv) {
-  if (VT == VT_DVB) {
-    d.c0 = *(const uint4*)pc;   // (w0 w1 w2 | codes 0-3; v.x = codes 4-7: dvb_codes puts them in place)
-  } else if (Vt<VT>::sliced) {
-    const uint3 t = *(const uint3*)pc;
-    d.c0.x = t.x;
-    d.c0.y = t.y;
-    d.c0.z = t.z;
-  } else {
-    d.c0 = *(const uint4*)pc;
-    if (sizeof(CT) == 4) d.c1 = *(const uint4*)(pc + 16);
-  }
-  load_values<VT>(d.v, pv);
-}
-
-template <typename CT, int VT>
-SGPU_DEV void load_chunk(DocChunk<CT, VT>& d, const uint8_t* rec, uint32_t len, uint32_t e0) {
-  const uint8_t *pc, *pv;
-  slice_ptrs<CT, VT>(rec, len, e0 >> 3, pc, pv);
-  load_slice<CT, VT>(d, pc, pv);
-}
-
-// The eight components of a lane's slice. Raw forms: unpacked. VT_DVB: the slice's first component and seven gaps ->
-// components, plus `bias` (the dense lookup table's LDS address, so that the results are the addresses to read; 0 for
-// the other layouts). `base` is passed through (the first r04 form chained the gaps across slices).
-template <typename CT, int VT>
-SGPU_DEV uint32_t slice_components(const DocChunk<CT, VT>& d, uint32_t base, uint32_t c[8], uint32_t bias = 0) {
-  if (Vt<VT>::sliced) {
-    const uint32_t w0 = d.c0.x, w1 = d.c0.y, w2 = d.c0.z;
-    uint32_t run = (w0 & 0xffffu) + bias;
-    c[0] = run;
-    run += (w0 >> 16) & 0xfffu;
-    c[1] = run;
-    run += ((w0 >> 28) | (w1 << 4)) & 0xfffu;
-    c[2] = run;
-    run += (w1 >> 8) & 0xfffu;
-    c[3] = run;
-    run += (w1 >> 20) & 0x7ffu;
-    c[4] = run;
-    run += ((w1 >> 31) | (w2 << 1)) & 0x7ffu;
-    c[5] = run;
-    run += (w2 >> 10) & 0x7ffu;
-    c[6] = run;
-    run += w2 >> 21;
-    c[7] = run;
-    return base;
-  }
-  if (sizeof(CT) == 2) {
-    c[0] = d.c0.x & 0xffffu; c[1] = d.c0.x >> 16; c[2] = d.c0.y & 0xffffu; c[3] = d.c0.y >> 16;
-    c[4] = d.c0.z & 0xffffu; c[5] = d.c0.z >> 16; c[6] = d.c0.w & 0xffffu; c[7] = d.c0.w >> 16;
-  } else {
-    c[0] = d.c0.x; c[1] = d.c0.y; c[2] = d.c0.z; c[3] = d.c0.w;
-    c[4] = d.c1.x; c[5] = d.c1.y; c[6] = d.c1.z; c[7] = d.c1.w;
-  }
-  return base;
-}
-
-// VT_DVB with the dense lookup table: slice_components is asked for table ADDRESSES (components + the table's LDS address)
+// VT_DVB with the dense lookup table: slice_components is asked for table ADDRESSES (components + the table's LDS address,
+// Lds::idx0), so that the running sums of the gaps ARE the addresses of the bytes to read
 template <int LK, int VT>
 SGPU_DEV uint32_t dvb_bias(const Lds& s) { return (Vt<VT>::sliced && LK == LK_DENSE) ? s.idx0 : 0u; }
 
@@ -989,41 +861,20 @@ SGPU_DEV float accumulate_chunk(const Lds& s, const DocChunk<CT, VT>& d, const u
   return acc;
 }
 
-// One pass (8 elements per lane) of one document by its 16-lane group, for the loops that take a document at a time
-// (cooperative rounds): `raw` = a VT_DVB index keeps this document in the VT_U8 record form.
-template <typename CT, int VT>
-SGPU_DEV void load_pass(DocChunk<CT, VT>& d, const uint8_t* rec, uint32_t len, bool raw, uint32_t e) {
-  const uint32_t sl = (e < len ? e : 0u) >> 3;   // lanes past the end re-read the first slice
-  const uint8_t *pc, *pv;
-  if (Vt<VT>::sliced && raw) {
-    slice_ptrs<CT, Vt<VT>::raw>(rec, len, sl, pc, pv);
-    d.c0 = *(const uint4*)pc;
-    load_values<Vt<VT>::raw>(d.v, pv);
-  } else {
-    slice_ptrs<CT, VT>(rec, len, sl, pc, pv);
-    load_slice<CT, VT>(d, pc, pv);
-  }
-}
+// One pass (record.hpp: load_pass) of one document scored by its 16-lane group, for the loops that take a document at a
+// time (cooperative rounds) and for every pass of a VT_DVB document.
 template <typename CT, int LK, int VT, bool SC>
-SGPU_DEV float score_pass(const Lds& s, const DocChunk<CT, VT>& d, bool raw, uint32_t e, uint32_t len, uint32_t& base, float a) {
+SGPU_DEV float score_pass(const Lds& s, const DocChunk<CT, VT>& d, bool raw, uint32_t e, uint32_t len, float a) {
   uint32_t c[8];
   const uint32_t bias = dvb_bias<LK, VT>(s);
   if (Vt<VT>::sliced && raw) {
-    c[0] = (d.c0.x & 0xffffu) + bias; c[1] = (d.c0.x >> 16) + bias; c[2] = (d.c0.y & 0xffffu) + bias; c[3] = (d.c0.y >> 16) + bias;
-    c[4] = (d.c0.z & 0xffffu) + bias; c[5] = (d.c0.z >> 16) + bias; c[6] = (d.c0.w & 0xffffu) + bias; c[7] = (d.c0.w >> 16) + bias;
+    raw_pass_components<CT, VT>(d, c, bias);
   } else {
-    base = slice_components<CT, VT>(d, base, c, bias);
+    slice_components<CT, VT>(d, c, bias);
   }
-  if (VT == VT_DVB) {
-    // the eight codes: a packed slice keeps codes 0-3 behind its gaps (c0.w) and codes 4-7 in the dword v.x; a raw
-    // record's codes are v.x, v.y as loaded
-    DocChunk<CT, VT> t = d;
-    t.v.x = raw ? d.v.x : d.c0.w;
-    t.v.y = raw ? d.v.y : d.v.x;
-    if (e < len) a = accumulate_chunk<CT, LK, VT, SC>(s, t, c, e, len, a);
-    return a;
-  }
-  if (e < len) a = accumulate_chunk<CT, LK, VT, SC>(s, d, c, e, len, a);
+  DocChunk<CT, VT> t = d;
+  place_values<CT, VT>(t, raw);
+  if (e < len) a = accumulate_chunk<CT, LK, VT, SC>(s, t, c, e, len, a);
   return a;
 }
 
@@ -1317,15 +1168,14 @@ SGPU_DEV void score_class(const Lds& s, const DevView& ix, const ChunkBufs& cb, 
   };
   auto consume = [&](int u) {
     float a = 0.0f;
-    uint32_t base = 0;   // (VT_DVB) the component before the pass's first element
 #pragma unroll
     for (int h = 0; h < NS; ++h) {
       if (Vt<VT>::sliced) {   // (per document: packed slice or raw components)
-        a = score_pass<CT, LK, VT, SC>(s, d[u][h], rawf[u], e0 + 128u * h, len[u], base, a);
+        a = score_pass<CT, LK, VT, SC>(s, d[u][h], rawf[u], e0 + 128u * h, len[u], a);
         continue;
       }
       uint32_t c[8];
-      base = slice_components<CT, VT>(d[u][h], base, c, dvb_bias<LK, VT>(s));
+      slice_components<CT, VT>(d[u][h], c, dvb_bias<LK, VT>(s));
       if (e0 + 128u * h < len[u]) a = accumulate_chunk<CT, LK, VT, SC>(s, d[u][h], c, e0 + 128u * h, len[u], a);
     }
     if (NS > 1) {
@@ -1335,12 +1185,12 @@ SGPU_DEV void score_class(const Lds& s, const DevView& ix, const ChunkBufs& cb, 
         DocChunk<CT, VT> t;
         if (Vt<VT>::sliced) {
           load_pass<CT, VT>(t, rec[u], len[u], rawf[u], e);
-          a = score_pass<CT, LK, VT, SC>(s, t, rawf[u], e, len[u], base, a);
+          a = score_pass<CT, LK, VT, SC>(s, t, rawf[u], e, len[u], a);
           continue;
         }
         load_chunk<CT, VT>(t, rec[u], len[u], e < len[u] ? e : 0u);
         uint32_t c[8];
-        base = slice_components<CT, VT>(t, base, c, dvb_bias<LK, VT>(s));
+        slice_components<CT, VT>(t, c, dvb_bias<LK, VT>(s));
         if (e < len[u]) a = accumulate_chunk<CT, LK, VT, SC>(s, t, c, e, len[u], a);
       }
     }
@@ -1611,15 +1461,14 @@ SGPU_DEV void score_stream_class(const Lds& s, const DevView& ix, const Ring& rg
   };
   auto consume = [&](int u) {
     float a = 0.0f;
-    uint32_t base = 0;
 #pragma unroll
     for (int h = 0; h < NS; ++h) {
       if (Vt<VT>::sliced) {
-        a = score_pass<CT, LK, VT, SC>(s, d[u][h], rawf[u], e0 + 128u * h, len[u], base, a);
+        a = score_pass<CT, LK, VT, SC>(s, d[u][h], rawf[u], e0 + 128u * h, len[u], a);
         continue;
       }
       uint32_t c[8];
-      base = slice_components<CT, VT>(d[u][h], base, c, dvb_bias<LK, VT>(s));
+      slice_components<CT, VT>(d[u][h], c, dvb_bias<LK, VT>(s));
       if (e0 + 128u * h < len[u]) a = accumulate_chunk<CT, LK, VT, SC>(s, d[u][h], c, e0 + 128u * h, len[u], a);
     }
     if (NS > 1) {
@@ -1628,12 +1477,12 @@ SGPU_DEV void score_stream_class(const Lds& s, const DevView& ix, const Ring& rg
         DocChunk<CT, VT> t;
         if (Vt<VT>::sliced) {
           load_pass<CT, VT>(t, rec[u], len[u], rawf[u], e);
-          a = score_pass<CT, LK, VT, SC>(s, t, rawf[u], e, len[u], base, a);
+          a = score_pass<CT, LK, VT, SC>(s, t, rawf[u], e, len[u], a);
           continue;
         }
         load_chunk<CT, VT>(t, rec[u], len[u], e < len[u] ? e : 0u);
         uint32_t c[8];
-        base = slice_components<CT, VT>(t, base, c, dvb_bias<LK, VT>(s));
+        slice_components<CT, VT>(t, c, dvb_bias<LK, VT>(s));
         if (e < len[u]) a = accumulate_chunk<CT, LK, VT, SC>(s, t, c, e, len[u], a);
       }
     }
@@ -2334,14 +2183,13 @@ SGPU_DEV bool coop_work(const Lds& s, const DevView& ix, const BatchView& qb, co
 #pragma unroll
         for (int u = 0; u < ND; ++u) {
           float a = 0.0f;
-          uint32_t base = 0;
-          a = sc ? score_pass<CT, LK, VT, true>(s, d[u], raw[u], e0, len[u], base, a)
-                 : score_pass<CT, LK, VT, false>(s, d[u], raw[u], e0, len[u], base, a);
+          a = sc ? score_pass<CT, LK, VT, true>(s, d[u], raw[u], e0, len[u], a)
+                 : score_pass<CT, LK, VT, false>(s, d[u], raw[u], e0, len[u], a);
           for (uint32_t eb = 128u; eb < len[u]; eb += 128u) {   // documents longer than 128 elements (trip count per group)
             DocChunk<CT, VT> t;
             load_pass<CT, VT>(t, rec[u], len[u], raw[u], eb + e0);
-            a = sc ? score_pass<CT, LK, VT, true>(s, t, raw[u], eb + e0, len[u], base, a)
-                   : score_pass<CT, LK, VT, false>(s, t, raw[u], eb + e0, len[u], base, a);
+            a = sc ? score_pass<CT, LK, VT, true>(s, t, raw[u], eb + e0, len[u], a)
+                   : score_pass<CT, LK, VT, false>(s, t, raw[u], eb + e0, len[u], a);
           }
           a = reduce16(a);
           spec += (sub == 0 && len[u] != 0);

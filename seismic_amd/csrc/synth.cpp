@@ -80,8 +80,7 @@ struct ClusterLaw {
 };
 static ClusterLaw cluster_law() {
   ClusterLaw l;
-  const char* t = std::getenv("SGPU_TEST_HOOKS");
-  const char* v = (t && *t && *t != '0') ? std::getenv("SGPU_SYNTH_CLUSTER") : nullptr;
+  const char* v = test_hooks_on() ? std::getenv("SGPU_SYNTH_CLUSTER") : nullptr;
   if (v) {
     unsigned g = 0;
     double a = 0, b = 0, c = 0;
