@@ -46,6 +46,15 @@ sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* ou
  * SGPU_EXACT_CAND_BYTES, read per call and honoured under the same switch, lowers that size. SGPU_EINVAL before the
  * replica's first exact call */
 sgpu_status sgpu_debug_exact_launches(sgpu_index* idx, uint32_t replica, uint32_t* out_launches);
+/* the posting arrays a search on `replica` walks, read back from the device: the replica's own (filter == NULL) or those of
+ * the filter's view there, which is obtained as a search obtains it - built on first use or after a new upload or graph,
+ * under the filter's mutex; no second build path. sizes5 = {block starts (n_blocks + 1), postings, kNN ids (0: no graph),
+ * bitmap words, allowed documents} - the last two 0 without a filter. A NULL buffer is skipped (all NULL: the sizes only); a
+ * buffer whose capacity (in elements; post_ref and post_doc share cap_postings) is below its array's size: SGPU_EINVAL.
+ * SGPU_EDEVICE when the index is not uploaded or the replica is out of range. One blocking copy per array, no state kept. */
+sgpu_status sgpu_debug_posting_view(sgpu_index* idx, const sgpu_filter* filter, uint32_t replica, uint32_t* out_block_post_start,
+                                    uint64_t cap_starts, uint64_t* out_post_ref, uint32_t* out_post_doc, uint64_t cap_postings,
+                                    uint32_t* out_knn, uint64_t cap_knn, uint32_t* out_bits, uint64_t cap_bits, uint64_t* sizes5);
 
 #ifdef __cplusplus
 }

@@ -238,6 +238,29 @@ class NativeIndex:
         mask of length n_docs. Pass it as filter= to search, batch_search, exact_search and exact_search_device."""
         return NativeFilter(self, ids)
 
+    def debug_posting_view(self, replica=0, filter=None):
+        """sgpu_debug_posting_view (a test hook: needs SGPU_TEST_HOOKS=1): the posting arrays a search on `replica` walks,
+        read back from the device, as a dict of numpy arrays - block_post_start u32 [n_blocks + 1], post_ref u64, post_doc u32,
+        knn u32 (empty without a graph); with a filter, those of its view there plus bits u32 and count."""
+        L = lib()
+        L.sgpu_debug_posting_view.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        fh = None if filter is None else _filter_handle(filter)
+        sizes = np.zeros(5, np.uint64)
+        check(L.sgpu_debug_posting_view(self.h, fh, int(replica), None, 0, None, None, 0, None, 0, None, 0, _p(sizes)))
+        n_starts, n_post, n_knn, n_bits = (int(x) for x in sizes[:4])
+        bps, ref, doc = np.zeros(n_starts, np.uint32), np.zeros(max(n_post, 1), np.uint64), np.zeros(max(n_post, 1), np.uint32)
+        knn, bits = np.zeros(max(n_knn, 1), np.uint32), np.zeros(max(n_bits, 1), np.uint32)
+        got = np.zeros(5, np.uint64)
+        check(L.sgpu_debug_posting_view(self.h, fh, int(replica), _p(bps), n_starts, _p(ref), _p(doc), n_post, _p(knn), n_knn,
+                                        _p(bits), n_bits, _p(got)))
+        if not np.array_equal(got, sizes):
+            raise RuntimeError("the view changed between the two calls: sizes %s, then %s" % (sizes, got))
+        out = dict(block_post_start=bps, post_ref=ref[:n_post], post_doc=doc[:n_post], knn=knn[:n_knn])
+        if filter is not None:
+            out.update(bits=bits[:n_bits], count=int(sizes[4]))
+        return out
+
     def stream_stats(self):
         """(documents, elements) a DotVByte index keeps in the raw record form; (0, 0) for the other value types."""
         a, b = C.c_uint64(0), C.c_uint64(0)
@@ -454,6 +477,11 @@ class NativeFilter:
 
     def device_bytes(self):
         return int(lib().sgpu_filter_device_bytes(self.h))
+
+    def debug_view(self, replica=0):
+        """The filter's view on `replica` read back from the device (NativeIndex.debug_posting_view with this filter): it
+        is built there first if a search has not done so yet."""
+        return self.index.debug_posting_view(replica, filter=self)
 
     def close(self):
         if self.h:

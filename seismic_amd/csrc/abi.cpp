@@ -75,6 +75,9 @@ uint64_t filter_count(const sgpu_filter* f);
 uint64_t filter_device_bytes(const sgpu_filter* f);
 void filter_destroy(sgpu_filter* f);
 bool filter_build_times(const sgpu_filter* f, uint32_t replica, double* out2);
+sgpu_status debug_posting_view(sgpu_index* idx, const sgpu_filter* f, uint32_t replica, uint32_t* out_bps, uint64_t cap_bps,
+                               uint64_t* out_ref, uint32_t* out_doc, uint64_t cap_post, uint32_t* out_knn, uint64_t cap_knn,
+                               uint32_t* out_bits, uint64_t cap_bits, uint64_t* sizes5);
 }  // namespace sgpu
 
 using namespace sgpu;
@@ -893,6 +896,20 @@ sgpu_status sgpu_debug_filter_build_times(const sgpu_filter* filter, uint32_t re
   if (!filter || !out2) return fail(SGPU_EINVAL, "null argument");
   if (!filter_build_times(filter, replica, out2)) return fail(SGPU_EINVAL, "the filter has no view on replica %u", replica);
   return SGPU_OK;
+}
+
+// (not part of the boundary: the posting arrays a search on `replica` walks, read back from the device - the replica's own
+// (filter == null) or those of the filter's view there, built as a search builds it on first use (filter.hip:
+// debug_posting_view). tests/test_gpu_filter_view.py compares all of them with a numpy compaction)
+sgpu_status sgpu_debug_posting_view(sgpu_index* idx, const sgpu_filter* filter, uint32_t replica, uint32_t* out_block_post_start,
+                                    uint64_t cap_starts, uint64_t* out_post_ref, uint32_t* out_post_doc, uint64_t cap_postings,
+                                    uint32_t* out_knn, uint64_t cap_knn, uint32_t* out_bits, uint64_t cap_bits, uint64_t* sizes5) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !sizes5) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status st = foreign_filter(idx, filter);
+  if (st != SGPU_OK) return st;
+  return debug_posting_view(idx, filter, replica, out_block_post_start, cap_starts, out_post_ref, out_post_doc, cap_postings,
+                            out_knn, cap_knn, out_bits, cap_bits, sizes5);
 }
 
 }  // extern "C"

@@ -154,6 +154,7 @@ struct FilterView {
   uint64_t generation = 0;
   std::vector<void*> allocs;
   uint64_t bytes = 0;
+  uint64_t n_kept = 0;       // postings of the view: what the scan counted, the size post_ref' and post_doc' were allocated with
   float build_ms = 0;        // device time of the build (events around its copies and kernels)
   double build_wall_ms = 0;  // wall time of the build, allocations included
 };
@@ -325,15 +326,16 @@ static sgpu_status view_build(const sgpu_filter* f, const DeviceIndex* d, uint64
   v->pub.view.block_post_start = bps;
   v->pub.view.post_ref = ref;
   v->pub.view.post_doc = doc;
+  v->n_kept = total;
   if (knn) v->pub.view.knn = knn;
   v->pub.bits = bits;
   v->build_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return SGPU_OK;
 }
 
-sgpu_status filter_view(const sgpu_filter* f, uint32_t replica, const FilterDeviceView** out) {
+// The view on `replica`, built if it is not there or stale; f->mu is held by the caller.
+static sgpu_status view_locked(const sgpu_filter* f, uint32_t replica, const FilterView** out) {
   const sgpu_index* idx = f->idx;
-  std::lock_guard<std::mutex> lk(f->mu);
   if (replica >= idx->replicas.size())
     return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
   const uint64_t gen = idx->generation.load(std::memory_order_acquire);
@@ -365,7 +367,57 @@ sgpu_status filter_view(const sgpu_filter* f, uint32_t replica, const FilterDevi
     }
     f->views[replica] = v;
   }
-  *out = &f->views[replica]->pub;
+  *out = f->views[replica];
+  return SGPU_OK;
+}
+
+sgpu_status filter_view(const sgpu_filter* f, uint32_t replica, const FilterDeviceView** out) {
+  std::lock_guard<std::mutex> lk(f->mu);
+  const FilterView* v = nullptr;
+  const sgpu_status st = view_locked(f, replica, &v);
+  if (st == SGPU_OK) *out = &v->pub;
+  return st;
+}
+
+// (test hook sgpu_debug_posting_view) The posting arrays a search on `replica` walks, copied to the host: the replica's own
+// (f == null) or those of f's view there, which is obtained as a search obtains it - built on first use - and read under
+// the filter's mutex. sizes5 = {block starts, postings, kNN ids, bitmap words, allowed documents} (the last two 0 without
+// a filter); a null buffer is skipped, one smaller than its array is an error. One blocking copy per array.
+sgpu_status debug_posting_view(sgpu_index* idx, const sgpu_filter* f, uint32_t replica, uint32_t* out_bps, uint64_t cap_bps,
+                               uint64_t* out_ref, uint32_t* out_doc, uint64_t cap_post, uint32_t* out_knn, uint64_t cap_knn,
+                               uint32_t* out_bits, uint64_t cap_bits, uint64_t* sizes5) {
+  if (replica >= idx->replicas.size())
+    return fail(SGPU_EDEVICE, "index is not uploaded to a device (call sgpu_index_upload) / replica out of range");
+  std::unique_lock<std::mutex> lk;
+  const DevView* view = &device_index_view(idx->replicas[replica]);
+  const uint32_t* bits = nullptr;
+  uint64_t n_post = idx->host.n_postings(), n_bits = 0, count = 0;
+  if (f) {
+    lk = std::unique_lock<std::mutex>(f->mu);
+    const FilterView* v = nullptr;
+    const sgpu_status st = view_locked(f, replica, &v);
+    if (st != SGPU_OK) return st;
+    view = &v->pub.view;
+    bits = v->pub.bits;
+    n_post = v->n_kept;
+    n_bits = f->bits.size();
+    count = v->pub.count;
+  }
+  const uint64_t n_starts = idx->host.n_blocks() + 1, n_knn = view->knn ? view->knn_total : 0;
+  sizes5[0] = n_starts;
+  sizes5[1] = n_post;
+  sizes5[2] = n_knn;
+  sizes5[3] = n_bits;
+  sizes5[4] = count;
+  if ((out_bps && cap_bps < n_starts) || ((out_ref || out_doc) && cap_post < n_post) || (out_knn && cap_knn < n_knn) ||
+      (out_bits && cap_bits < n_bits))
+    return fail(SGPU_EINVAL, "buffer too small");
+  HIP_TRY(hipSetDevice(device_index_device(idx->replicas[replica])));
+  if (out_bps) HIP_TRY(hipMemcpy(out_bps, view->block_post_start, n_starts * 4, hipMemcpyDeviceToHost));
+  if (out_ref && n_post) HIP_TRY(hipMemcpy(out_ref, view->post_ref, n_post * 8, hipMemcpyDeviceToHost));
+  if (out_doc && n_post) HIP_TRY(hipMemcpy(out_doc, view->post_doc, n_post * 4, hipMemcpyDeviceToHost));
+  if (out_knn && n_knn) HIP_TRY(hipMemcpy(out_knn, view->knn, n_knn * 4, hipMemcpyDeviceToHost));
+  if (out_bits && n_bits) HIP_TRY(hipMemcpy(out_bits, bits, n_bits * 4, hipMemcpyDeviceToHost));
   return SGPU_OK;
 }
 

@@ -239,3 +239,42 @@ def test_python_surface_on_the_toy_dataset():
     # a filter keeps its index alive
     g = seismic_amd.SeismicIndex.build(os.path.join(GOLD, "toy", "documents.jsonl"), upload=False).make_filter(allowed)
     assert g.count == f.count and g.index.len == n
+
+
+def test_the_posting_view_hook_is_a_test_hook(monkeypatch):
+    """sgpu_debug_posting_view: declared in the testing header only, SGPU_EINVAL without SGPU_TEST_HOOKS=1 (and nothing
+    written), SGPU_EDEVICE with it while the index is on no device, SGPU_EINVAL for a filter of another index."""
+    name = "sgpu_debug_posting_view"
+    assert re.search(r"\b%s\s*\(" % name, open(os.path.join(ROOT, "include", "seismic_hip_testing.h")).read())
+    assert name not in open(os.path.join(ROOT, "include", "seismic_hip.h")).read()
+    ix, other = _index(), _index(seed=12)
+    f, fo = ix.make_filter([1, 2, 3]), other.make_filter([1, 2, 3])
+    L = _native.lib()
+    vp = ctypes.c_void_p
+    L.sgpu_debug_posting_view.argtypes = [vp, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp,
+                                          ctypes.c_uint64, vp, ctypes.c_uint64, vp]
+
+    def call(filt):
+        sizes = np.full(5, 77, np.uint64)
+        return L.sgpu_debug_posting_view(ix.h, filt, 0, None, 0, None, None, 0, None, 0, None, 0, p(sizes)), sizes
+
+    for off in (None, "0", ""):
+        if off is None:
+            monkeypatch.delenv("SGPU_TEST_HOOKS")
+        else:
+            monkeypatch.setenv("SGPU_TEST_HOOKS", off)
+        for filt in (None, f.h, fo.h):
+            st, sizes = call(filt)
+            assert st == SGPU_EINVAL and "test hook" in _err() and (sizes == 77).all()
+    monkeypatch.setenv("SGPU_TEST_HOOKS", "1")
+    for filt in (None, f.h):
+        st, _ = call(filt)
+        assert st == SGPU_EDEVICE and "upload" in _err()
+    st, _ = call(fo.h)
+    assert st == SGPU_EINVAL and "another index" in _err()
+    with pytest.raises(_native.SeismicHipError) as e:
+        ix.debug_posting_view()
+    assert e.value.status == SGPU_EDEVICE
+    with pytest.raises(_native.SeismicHipError):
+        f.debug_view()
+    assert f.device_bytes() == 0 and _native.lib().sgpu_abi_version() == 4
