@@ -452,6 +452,47 @@ sgpu_status sgpu_rerank_documents_host(const sgpu_index* idx,
     const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, uint32_t num_threads,
     float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
 
+/* ---- explain: the terms behind a document's score -----------------------------
+ * A score is a sum of products over the vocabulary terms query and document share; this call returns, beside each
+ * candidate's score, the m largest of those products with their components and both weights. Queries and candidates
+ * are given exactly as for sgpu_score_documents (any order, repeats allowed, possibly none); candidate i is cand_ids[i]
+ * with its query, rows are numbered like the candidates (cand_off[nq] in all).
+ * Term: a stored element e < len(d) of the document whose component c the query carries with a weight w that is not
+ * +-0. Padding elements of a record are never terms; a stored value of 0 still makes a term.
+ * Product of a term: the f32 the score adds for that element, bit for bit - F16: fl(w * f32(value)); FIXEDU8 and
+ * DOTVBYTE: fl(fl(w * val_scale) * (float)code), where the inner product is exact because val_scale is a power of two
+ * (a w so small that fl(w * val_scale) underflows is outside this contract: a w whose scaled weight is +-0 counts as +-0).
+ * out_scores[i]    the bits sgpu_score_documents returns for the pair (the canonical order above): the call takes the
+ *                  score call's place when terms are wanted.
+ * out_n_terms[i]   all terms of the pair, however many are returned.
+ * Row i of the cand_off[nq] x m row-major out_comps, out_q_vals, out_d_vals, out_products holds the first
+ * min(m, out_n_terms[i]) terms in this order: ordered(product bits) descending, then component ascending, where
+ * ordered(b) is the monotone integer image of f32 bits (all bits of a negative flipped, the sign bit of the others
+ * set): the numeric order on finite products with -0.0 below +0.0. A document's components are distinct, so the order
+ * is total. Per term: the component, w as the caller gave it, the stored value as an f32 (binary16 widened, or
+ * code * val_scale; both exact) and the product. Slots past the filled ones are zero in all four arrays.
+ * Where m >= out_n_terms[i] the returned products, added at their elements' places in the canonical order, give
+ * out_scores[i]. Pairs with a score or product that is not finite (inf query values) need not match the host twin.
+ * Checks, in this order: null arguments (SGPU_EINVAL; every output pointer too, also when there is no candidate),
+ * everything sgpu_score_documents checks in its order, m == 0 (SGPU_EINVAL), m > 32 (SGPU_ELIMIT), index not uploaded or
+ * replica out of range (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays usable). nq == 0 or no candidate at
+ * all is SGPU_OK.
+ * The call shares the score calls' per-replica stream, mutex and recycled scratch and takes turns with them; it is safe
+ * beside searches. It adds no index array. SGPU_SCORE_CHUNK cuts it into launches as it cuts the score call (without it
+ * a launch takes as many candidates as 64 MiB of term rows hold, at most 2^20); the outputs do not depend on the cuts. */
+sgpu_status sgpu_explain_documents(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
+    float* out_scores, uint32_t* out_n_terms,
+    uint32_t* out_comps, float* out_q_vals, float* out_d_vals, float* out_products);
+/* The same on the host cores (needs no upload), bit-identical wherever scores and products are finite; the same checks
+ * without the device ones. num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_explain_documents_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, uint32_t num_threads,
+    float* out_scores, uint32_t* out_n_terms,
+    uint32_t* out_comps, float* out_q_vals, float* out_d_vals, float* out_products);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

@@ -90,6 +90,8 @@ def lib():
         L.sgpu_score_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.sgpu_rerank_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp]
         L.sgpu_rerank_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.sgpu_explain_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32] + [vp] * 6
+        L.sgpu_explain_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32] + [vp] * 6
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -435,6 +437,40 @@ class NativeIndex:
         check(lib().sgpu_rerank_documents_host(self.h, _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), k,
                                                int(num_threads), _p(sc), _p(ids), _p(n)))
         return sc[:nq], ids[:nq], n[:nq]
+
+    # ---- the terms behind each candidate's score ----
+    @staticmethod
+    def _explain_buffers(q_off, comps, vals, cand_off, cand_ids, m):
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        m = int(m)
+        if not 0 <= m < 2 ** 32:
+            raise ValueError("m = %d" % m)
+        n = len(cand_ids)
+        rows = (max(n, 1), m if 1 <= m <= 32 else 1)   # (an m the library refuses: nothing is written)
+        out = (np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.uint32), np.zeros(rows, np.uint32),
+               np.zeros(rows, np.float32), np.zeros(rows, np.float32), np.zeros(rows, np.float32))
+        cand = cand_ids if n else np.zeros(1, np.uint64)
+        return q_off, comps, vals, cand_off, cand, n, m, out
+
+    def explain_documents(self, q_off, comps, vals, cand_off, cand_ids, m, replica=0):
+        """sgpu_explain_documents: per candidate (given as for score_documents) its score, the number of terms query and
+        document share, and the m <= 32 best of them - product descending in the order of the f32 bits' integer image,
+        then component ascending -, computed on the device of `replica`. Returns (scores f32 [n], n_terms u32 [n],
+        components u32 [n, m], query weights f32 [n, m], document values f32 [n, m], products f32 [n, m]); slots past
+        min(m, n_terms) are zero."""
+        q_off, comps, vals, cand_off, cand, n, m, out = self._explain_buffers(q_off, comps, vals, cand_off, cand_ids, m)
+        check(lib().sgpu_explain_documents(self.h, int(replica), _p(q_off), _p(comps), _p(vals), len(q_off) - 1, _p(cand_off),
+                                           _p(cand), m, *[_p(a) for a in out]))
+        return tuple(a[:n] for a in out)
+
+    def explain_documents_host(self, q_off, comps, vals, cand_off, cand_ids, m, num_threads=0):
+        """sgpu_explain_documents_host: the same on the host cores (needs no upload), bit-identical."""
+        q_off, comps, vals, cand_off, cand, n, m, out = self._explain_buffers(q_off, comps, vals, cand_off, cand_ids, m)
+        check(lib().sgpu_explain_documents_host(self.h, _p(q_off), _p(comps), _p(vals), len(q_off) - 1, _p(cand_off), _p(cand),
+                                                m, int(num_threads), *[_p(a) for a in out]))
+        return tuple(a[:n] for a in out)
 
 
 def _filter_handle(f):

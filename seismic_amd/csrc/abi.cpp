@@ -66,6 +66,9 @@ sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint
 sgpu_status rerank_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                     const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
                                     float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
+sgpu_status explain_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                     const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
+                                     const ExplainOut& out);
 bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
@@ -868,7 +871,24 @@ sgpu_status sgpu_rerank_documents_host(const sgpu_index* idx, const uint64_t* q_
                                out_n);
 }
 
-// (not part of the boundary: what the last sgpu_score_documents / sgpu_rerank_documents call on `replica` measured - out8 =
+sgpu_status sgpu_explain_documents(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                   const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
+                                   float* out_scores, uint32_t* out_n_terms, uint32_t* out_comps, float* out_q_vals,
+                                   float* out_d_vals, float* out_products) {
+  const ExplainOut out{out_scores, out_n_terms, out_comps, out_q_vals, out_d_vals, out_products};
+  return explain_documents_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, m, out);
+}
+
+sgpu_status sgpu_explain_documents_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                        uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
+                                        uint32_t num_threads, float* out_scores, uint32_t* out_n_terms, uint32_t* out_comps,
+                                        float* out_q_vals, float* out_d_vals, float* out_products) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  const ExplainOut out{out_scores, out_n_terms, out_comps, out_q_vals, out_d_vals, out_products};
+  return explain_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, m, num_threads, out);
+}
+
+// (not part of the boundary: what the last sgpu_score_documents / sgpu_rerank_documents / sgpu_explain_documents call on `replica` measured - out8 =
 // {device ms of its score kernels, launches, 1 = dense table / 0 = hash table, grid, workgroup size, LDS bytes, device ms of
 // the selection kernels, merge rounds}; SGPU_EINVAL before the replica's first score call. tools/score_probe.py,
 // tools/rerank_probe.py)

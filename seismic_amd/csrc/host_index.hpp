@@ -108,6 +108,22 @@ sgpu_status rerank_check_args(const HostIndex& h, const uint64_t* q_off, const u
 sgpu_status rerank_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                   const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, uint32_t num_threads,
                                   float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
+// the m best terms behind each candidate's score (sgpu_explain_documents_host) and the checks both explain calls run
+constexpr uint32_t kExplainMaxTerms = 32;
+struct ExplainOut {   // the outputs of an explain call: one score and count per candidate, rows of m per term array
+  float* scores;
+  uint32_t* n_terms;
+  uint32_t* comps;
+  float* q_vals;
+  float* d_vals;
+  float* products;
+};
+sgpu_status explain_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                               const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, const ExplainOut& out,
+                               uint32_t* max_nnz);
+sgpu_status explain_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                   const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, uint32_t num_threads,
+                                   const ExplainOut& out);
 // score_documents.hip
 void score_state_free(ScoreState* s);
 

@@ -42,6 +42,10 @@
 //           keys goes to a smaller tier instead of being padded to C: 128 keys per wave64 (four tasks per workgroup, 28
 //           steps of one compare-exchange per lane: the 10 000 x 100 shape) or 512 keys per wave64. Every workgroup has
 //           256 threads; the barriers of the tiers' fixed step counts are uniform over it.
+//
+// sgpu_explain_documents runs through the same launcher (score_run: the staged queries, the tiles, the cuts into launches,
+// the per-replica stream, mutex and scratch) with explain_documents.hip's kernel in score_documents_kernel's place; what
+// the two kernels share is score_lookup.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -51,19 +55,15 @@
 #include <type_traits>
 #include <vector>
 
-#include "device_prims.hpp"
-#include "hip_util.hpp"
+#include "score_lookup.hpp"
 
 namespace sgpu {
 
 namespace {
 
-constexpr uint32_t kScoreTile = 128;             // candidates per tile
 constexpr uint32_t kScoreDocs = 2;               // candidates a 16-lane group has in flight
-constexpr uint32_t kScoreDenseLds = 128u << 10;  // the dense table is used where (dim + 1) floats fit this
 constexpr uint32_t kScoreChunk = 1u << 20;       // candidates per launch (SGPU_SCORE_CHUNK overrides)
-constexpr uint32_t kHashEmpty = 0xffffffffu;
-constexpr uint32_t kNoQuery = 0xffffffffu;
+constexpr uint64_t kExplainRowBytes = 64ull << 20;   // ... of an explain call: as many as this much of term rows holds
 
 struct ScoreArgs {
   const uint8_t* fwd;        // DevView::fwd (the document-major records lie at its start in both forward layouts)
@@ -79,23 +79,6 @@ struct ScoreArgs {
   uint32_t slot_bits;        // hash table: log2 of its slots
   float val_scale;
 };
-
-// the query's weight of component c (0.0: the query does not carry it). Dense: tab[c], c <= dim. Hash: linear probing
-// from the component's slot; the table is at most half full, so a probe sequence always meets an empty slot.
-template <bool DENSE>
-__device__ __forceinline__ float weight_of(const uint8_t* smem, uint32_t c, uint32_t slot_bits) {
-  if (DENSE) return ((const float*)smem)[c];
-  const uint32_t* keys = (const uint32_t*)smem;
-  const float* wts = (const float*)(smem + ((size_t)4u << slot_bits));
-  const uint32_t mask = (1u << slot_bits) - 1u;
-  uint32_t slot = (c * 2654435761u) >> (32u - slot_bits);
-  for (;;) {
-    const uint32_t k = keys[slot];
-    if (k == kHashEmpty) return 0.0f;
-    if (k == c) return wts[slot];
-    slot = (slot + 1u) & mask;
-  }
-}
 
 template <int CW, int VT, bool DENSE>
 __global__ __launch_bounds__(1024) void score_documents_kernel(ScoreArgs a) {
@@ -329,6 +312,7 @@ struct ScoreState {
   DeviceBuffer tiles, cand, scores;    // a launch's tiles, candidate ids and scores
   // rerank: a launch's selection tasks and k-key slots, the two carry slots, the call's rows (scores, ids, counts)
   DeviceBuffer sel_tasks, slots, carry, row_scores, row_ids, row_n;
+  DeviceBuffer terms;   // explain: a launch's term counts and its four arrays of rows
   std::vector<uint4> h_tiles;   // host staging of a launch
   std::vector<uint32_t> h_ids;
   std::vector<std::vector<SelTask>> sel_rounds;   // [round * tiers + tier]
@@ -344,7 +328,7 @@ void score_state_free(ScoreState* s) {
   if (s->device >= 0) (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (DeviceBuffer* b : {&s->q_off, &s->q_comp, &s->q_val, &s->tiles, &s->cand, &s->scores, &s->sel_tasks, &s->slots, &s->carry,
-                          &s->row_scores, &s->row_ids, &s->row_n})
+                          &s->row_scores, &s->row_ids, &s->row_n, &s->terms})
     b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -525,11 +509,18 @@ static sgpu_status rerank_rows_end(ScoreState* s, const RerankCall* rr, uint32_t
   return SGPU_OK;
 }
 
-// A score call (rr null: every candidate's score to out_scores) or a rerank call (rr: the selection follows each launch
-// on the stream, and the call's rows come back at the end).
+// An explain call: what it returns beyond a score call (null for the other calls).
+struct ExplainCall {
+  uint32_t m = 0;
+  ExplainOut out{};
+};
+
+// A score call (rr, ex null: every candidate's score to out_scores), a rerank call (rr: the selection follows each launch
+// on the stream, and the call's rows come back at the end) or an explain call (ex: explain_documents.hip's kernel in the
+// score kernel's place, each launch's scores and term rows to ex->out).
 static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
                              const float* vals, uint32_t nq, uint32_t max_nnz, const uint64_t* cand_off, const uint64_t* cand_ids,
-                             float* out_scores, RerankCall* rr = nullptr) {
+                             float* out_scores, RerankCall* rr = nullptr, const ExplainCall* ex = nullptr) {
   HIP_TRY(hipSetDevice(s->device));
   s->last_kernel_ms = 0;
   s->last_launches = 0;
@@ -548,13 +539,18 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
   const uint32_t lds = dense ? (uint32_t)dense_bytes : (8u << slot_bits);
   const uint32_t block = lds > (40u << 10) ? 1024u : (lds > (20u << 10) ? 512u : 256u);
   ScoreKernel kern = score_kernel(h.comp_width, h.value_type, dense);
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)block, lds));
+  if (ex) {
+    const sgpu_status fst = explain_kernel_fit(h.comp_width, h.value_type, dense, block, lds, &per_cu);
+    if (fst != SGPU_OK) return fst;
+  } else {
+    HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)block, lds));
+  }
   if (per_cu < 1) return fail(SGPU_ELIMIT, "the score kernel does not fit on a CU (%u bytes of LDS)", lds);
   per_cu = std::min(per_cu, (int)(2048u / block));
 
-  uint64_t budget = kScoreChunk;
+  uint64_t budget = ex ? std::min<uint64_t>(kScoreChunk, kExplainRowBytes / (16ull * ex->m)) : kScoreChunk;
   if (const char* v = std::getenv("SGPU_SCORE_CHUNK"))
     if (*v) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
   budget = std::min<uint64_t>(budget, 1ull << 28);
@@ -583,6 +579,12 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
   s->last_block = block;
   s->last_lds = lds;
 
+  ExplainArgs xa{};
+  if (ex) {
+    xa.fwd = a.fwd, xa.doc_ref = a.doc_ref, xa.q_off = a.q_off, xa.q_comp = a.q_comp, xa.q_val = a.q_val;
+    xa.dim = a.dim, xa.slot_bits = a.slot_bits, xa.val_scale = a.val_scale, xa.m = ex->m;
+  }
+
   SelArgs sel{};
   if (rr && (st = rerank_rows_begin(s, rr, nq, &sel)) != SGPU_OK) return st;
 
@@ -606,6 +608,8 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
     if ((st = score_reserve(s, s->tiles, s->h_tiles.size() * sizeof(uint4))) != SGPU_OK ||
         (st = score_reserve(s, s->cand, n_cand * 4)) != SGPU_OK || (st = score_reserve(s, s->scores, n_cand * 4)) != SGPU_OK)
       return st;
+    const uint64_t cells = ex ? n_cand * ex->m : 0;   // of each of a launch's four term arrays, behind its n_cand counts
+    if (ex && (st = score_reserve(s, s->terms, (n_cand + 4 * cells) * 4)) != SGPU_OK) return st;
     HIP_TRY(hipMemcpyAsync(s->tiles.p, s->h_tiles.data(), s->h_tiles.size() * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->cand.p, s->h_ids.data(), n_cand * 4, hipMemcpyHostToDevice, s->stream));
     a.tiles = s->tiles.as<const uint4>();
@@ -615,10 +619,28 @@ static sgpu_status score_run(ScoreState* s, const HostIndex& h, const DevView& v
     const uint32_t grid = (uint32_t)std::min<uint64_t>(a.n_tiles, (uint64_t)s->n_cu * (uint32_t)per_cu);
     s->last_grid = grid;
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s->stream, a);
-    HIP_TRY(hipGetLastError());
+    if (ex) {
+      xa.tiles = a.tiles, xa.cand = a.cand, xa.n_tiles = a.n_tiles, xa.scores = a.out;
+      xa.n_terms = s->terms.as<uint32_t>();
+      xa.comps = xa.n_terms + n_cand;
+      xa.q_vals = (float*)(xa.comps + cells);
+      xa.d_vals = xa.q_vals + cells;
+      xa.products = xa.d_vals + cells;
+      if ((st = explain_kernel_launch(h.comp_width, h.value_type, dense, grid, block, lds, s->stream, xa)) != SGPU_OK) return st;
+    } else {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s->stream, a);
+      HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
-    if (!rr) {
+    if (ex) {
+      const uint64_t r0 = first * ex->m;
+      HIP_TRY(hipMemcpyAsync(ex->out.scores + first, s->scores.p, n_cand * 4, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(ex->out.n_terms + first, xa.n_terms, n_cand * 4, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(ex->out.comps + r0, xa.comps, cells * 4, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(ex->out.q_vals + r0, xa.q_vals, cells * 4, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(ex->out.d_vals + r0, xa.d_vals, cells * 4, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(ex->out.products + r0, xa.products, cells * 4, hipMemcpyDeviceToHost, s->stream));
+    } else if (!rr) {
       HIP_TRY(hipMemcpyAsync(out_scores + first, s->scores.p, n_cand * 4, hipMemcpyDeviceToHost, s->stream));
     } else if ((st = rerank_select(s, rr, sel, cand_off, nq, s->h_tiles.front().x, first, pos)) != SGPU_OK) {
       return st;
@@ -689,6 +711,29 @@ sgpu_status rerank_documents_device(sgpu_index* idx, uint32_t replica, const uin
   try {
     return score_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, max_nnz, cand_off, cand_ids,
                      nullptr, &rr);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+sgpu_status explain_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                     const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
+                                     const ExplainOut& out) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  uint32_t max_nnz = 0;
+  const sgpu_status vst = explain_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, m, out, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  ScoreState* s = nullptr;
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
+  if (nq == 0 || cand_off[nq] == 0) return SGPU_OK;
+  ExplainCall ex;
+  ex.m = m;
+  ex.out = out;
+  std::lock_guard<std::mutex> lk(s->mu);
+  try {
+    return score_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, max_nnz, cand_off, cand_ids,
+                     nullptr, nullptr, &ex);
   } catch (const std::bad_alloc&) {
     return fail(SGPU_ENOMEM, "out of host memory");
   }

@@ -1,5 +1,5 @@
-// score_host.cpp — sgpu_score_documents_host and sgpu_rerank_documents_host, and the argument checks they share with
-// the device calls.
+// score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host and sgpu_explain_documents_host, and the
+// argument checks they share with the device calls.
 //
 // The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
@@ -160,6 +160,125 @@ sgpu_status rerank_documents_host(const HostIndex& h, const uint64_t* q_off, con
       out_doc_ids[(size_t)q * k + i] = it[i].id;
     }
     out_n[q] = (uint32_t)n;
+  }
+  return SGPU_OK;
+}
+
+// Checks 1 - 4 of sgpu_explain_documents, in the header's order.
+sgpu_status explain_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                               const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, const ExplainOut& out,
+                               uint32_t* max_nnz) {
+  if (!out.scores || !out.n_terms || !out.comps || !out.q_vals || !out.d_vals || !out.products) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out.scores, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (m == 0) return fail(SGPU_EINVAL, "m must be at least 1");
+  if (m > kExplainMaxTerms) return fail(SGPU_ELIMIT, "m = %u (explaining documents: limit %u)", m, kExplainMaxTerms);
+  return SGPU_OK;
+}
+
+namespace {
+inline uint32_t f32_bits(float x) {
+  uint32_t b;
+  std::memcpy(&b, &x, 4);
+  return b;
+}
+// the monotone integer image of an f32 (device_prims.hpp: ordered_u32) and its inverse
+inline uint32_t ordered_bits(float x) {
+  const uint32_t b = f32_bits(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+inline float ordered_bits_inv(uint32_t k) {
+  const uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float x;
+  std::memcpy(&x, &b, 4);
+  return x;
+}
+struct Term {
+  uint64_t key;   // ordered(product) << 32 | ~component: a larger key is an earlier term
+  uint64_t at;    // the element's place in the forward arrays
+};
+}  // namespace
+
+// score_one that also collects the pair's terms: the elements whose component has a table weight that is not +-0.
+static inline float explain_one(const HostIndex& h, uint64_t doc, const float* dense, std::vector<Term>& terms) {
+  const uint64_t s = h.fwd_offsets[doc], e = h.fwd_offsets[doc + 1];
+  float t[16];
+  for (int j = 0; j < 16; ++j) t[j] = 0.0f;
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+  terms.clear();
+  for (uint64_t i = s; i < e; ++i) {
+    const float v = f16 ? f16_to_f32(h.fwd_vals[i]) : (float)h.fwd_codes[i];
+    const int lane = (int)(((i - s) >> 3) & 15);
+    const uint32_t c = h.comp(i);
+    const float p = dense[c] * v;
+    t[lane] = t[lane] + p;
+    if (f32_bits(dense[c]) & 0x7fffffffu) terms.push_back(Term{((uint64_t)ordered_bits(p) << 32) | (uint64_t)(~c), i});
+  }
+  for (int st = 8; st >= 1; st >>= 1) {
+    float u[16];
+    for (int j = 0; j < 16; ++j) u[j] = t[j] + t[j ^ st];
+    for (int j = 0; j < 16; ++j) t[j] = u[j];
+  }
+  return t[0];
+}
+
+// The host twin of explain_documents.hip, the arbiter of its rows: a plain loop over the pairs, the score accumulated as
+// score_one does, the terms ordered by their keys and cut to m.
+sgpu_status explain_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                   const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, uint32_t num_threads,
+                                   const ExplainOut& out) {
+  uint32_t max_nnz = 0;
+  const sgpu_status vst = explain_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, m, out, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0 || cand_off[nq] == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  uint64_t longest = 0;
+  for (uint64_t i = 0; i < cand_off[nq]; ++i) longest = std::max(longest, h.fwd_offsets[cand_ids[i] + 1] - h.fwd_offsets[cand_ids[i]]);
+  std::vector<std::vector<float>> tables;
+  std::vector<std::vector<Term>> found;
+  try {
+    tables.assign((size_t)team, std::vector<float>());
+    for (auto& t : tables) t.assign(h.dim, 0.0f);
+    found.assign((size_t)team, std::vector<Term>());
+    for (auto& v : found) v.reserve(longest);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+    if (cand_off[q + 1] == cand_off[q]) continue;
+#ifdef _OPENMP
+    const size_t me = (size_t)omp_get_thread_num();
+#else
+    const size_t me = 0;
+#endif
+    float* dense = tables[me].data();
+    std::vector<Term>& terms = found[me];   // (reserved for the longest document: nothing below allocates)
+    const uint32_t *qc0 = comps + q_off[q], *qc1 = comps + q_off[q + 1];
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
+      out.scores[i] = explain_one(h, cand_ids[i], dense, terms);
+      out.n_terms[i] = (uint32_t)terms.size();
+      const size_t n = std::min<size_t>(m, terms.size());
+      std::partial_sort(terms.begin(), terms.begin() + (ptrdiff_t)n, terms.end(),
+                        [](const Term& a, const Term& b) { return a.key > b.key; });
+      for (size_t r = 0; r < m; ++r) {
+        const size_t o = (size_t)i * m + r;
+        if (r < n) {
+          const uint32_t c = ~(uint32_t)terms[r].key;
+          out.comps[o] = c;
+          out.q_vals[o] = vals[q_off[q] + (uint64_t)(std::lower_bound(qc0, qc1, c) - qc0)];   // (w as given, not the table's)
+          out.d_vals[o] = h.val(terms[r].at);
+          out.products[o] = ordered_bits_inv((uint32_t)(terms[r].key >> 32));
+        } else {
+          out.comps[o] = 0;
+          out.q_vals[o] = out.d_vals[o] = out.products[o] = 0.0f;
+        }
+      }
+    }
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
   }
   return SGPU_OK;
 }

@@ -1,0 +1,61 @@
+// score_lookup.hpp — what the kernels that score caller-given documents share (score_documents_kernel in
+// score_documents.hip, explain_documents_kernel in explain_documents.hip): the tile, the form of the query's weight table
+// in LDS and its lookup; and what score_documents.hip, which runs both kinds of call, sees of explain_documents.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "device_prims.hpp"
+#include "hip_util.hpp"
+
+namespace sgpu {
+
+constexpr uint32_t kScoreTile = 128;             // candidates per tile
+constexpr uint32_t kScoreDenseLds = 128u << 10;  // the dense table is used where (dim + 1) floats fit this
+constexpr uint32_t kHashEmpty = 0xffffffffu;
+constexpr uint32_t kNoQuery = 0xffffffffu;
+
+// the query's weight of component c (0.0: the query does not carry it). Dense: tab[c], c <= dim. Hash: linear probing
+// from the component's slot; the table is at most half full, so a probe sequence always meets an empty slot.
+template <bool DENSE>
+__device__ __forceinline__ float weight_of(const uint8_t* smem, uint32_t c, uint32_t slot_bits) {
+  if (DENSE) return ((const float*)smem)[c];
+  const uint32_t* keys = (const uint32_t*)smem;
+  const float* wts = (const float*)(smem + ((size_t)4u << slot_bits));
+  const uint32_t mask = (1u << slot_bits) - 1u;
+  uint32_t slot = (c * 2654435761u) >> (32u - slot_bits);
+  for (;;) {
+    const uint32_t k = keys[slot];
+    if (k == kHashEmpty) return 0.0f;
+    if (k == c) return wts[slot];
+    slot = (slot + 1u) & mask;
+  }
+}
+
+// ---- explain_documents.hip ----
+struct ExplainArgs {
+  const uint8_t* fwd;        // as ScoreArgs (score_documents.hip): the index, the call's staged queries, a launch's tiles and ids
+  const uint64_t* doc_ref;
+  const uint64_t* q_off;
+  const uint32_t* q_comp;
+  const float* q_val;
+  const uint4* tiles;
+  const uint32_t* cand;
+  float* scores;             // per candidate of the launch: its score and the number of its terms
+  uint32_t* n_terms;
+  uint32_t* comps;           // rows of m per candidate of the launch
+  float* q_vals;
+  float* d_vals;
+  float* products;
+  uint32_t n_tiles;
+  uint32_t dim;
+  uint32_t slot_bits;
+  uint32_t m;
+  float val_scale;
+};
+// the explain kernel of (component width, value type, lookup form): workgroups of `block` threads with `lds` bytes of
+// table that fit a CU (sets the kernel's LDS attribute), and its launch
+sgpu_status explain_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t block, uint32_t lds, int* per_cu);
+sgpu_status explain_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t stream,
+                                  const ExplainArgs& a);
+
+}  // namespace sgpu

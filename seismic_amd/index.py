@@ -318,7 +318,8 @@ class _ScoreMixin:
     best of them (sgpu_score_documents, sgpu_rerank_documents; no reference counterpart - the reference computes such a score only inside its search,
     QueryEvaluator::compute_distance at src/posting_list.rs:210-211). A score is what search returns for the document,
     bit for bit. The classes supply _score_queries (queries -> CSR, unknown tokens dropped as in search),
-    _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id)."""
+    _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id);
+    explain / batch_explain (sgpu_explain_documents: the terms behind a score) also _score_token (component -> token)."""
 
     def _score_csr(self, query_components, query_values, doc_ids_per_query):
         off, comps, vals = self._score_queries(query_components, query_values)
@@ -379,6 +380,29 @@ class _ScoreMixin:
         """The k best of the documents `doc_ids` for one query -> [(score, doc_id)], best first."""
         return self.batch_rerank([query_components], [query_values], [doc_ids], k, device)[0]
 
+    def batch_explain(self, query_components, query_values, doc_ids_per_query, m=10, device=None):
+        """Per query and document of doc_ids_per_query[q] (as for batch_score) -> (score, n_terms, [(token, query weight,
+        document weight, product)]): the score batch_score returns, the number of terms query and document share, and the
+        m best of them (1 <= m <= 32), largest product first, ties by component ascending. The score is the sum of all
+        n_terms products in the library's summation order. Tokens are mapped back through _score_token (the token string;
+        the raw classes: the integer component). sgpu_explain_documents on the GPU the index is on (device None) or its
+        host twin (device False)."""
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        if self._score_on_device(device):
+            out = self._ix.explain_documents(off, comps, vals, cand_off, cand, m)
+        else:
+            out = self._ix.explain_documents_host(off, comps, vals, cand_off, cand, m)
+        sc, nt, tc, tq, td, tp = [a.tolist() for a in out]
+        token = self._score_token
+        docs = [(sc[i], nt[i], [(token(c), q, d, p) for c, q, d, p in list(zip(tc[i], tq[i], td[i], tp[i]))[:nt[i]]])
+                for i in range(len(sc))]
+        bounds = cand_off.astype(np.int64).tolist()
+        return [docs[bounds[i]:bounds[i + 1]] for i in range(len(rows))]
+
+    def explain(self, query_components, query_values, doc_ids, m=10, device=None):
+        """(score, n_terms, [(token, query weight, document weight, product)]) of each of `doc_ids` for one query."""
+        return self.batch_explain([query_components], [query_values], [doc_ids], m, device)[0]
+
     def _batch_rerank_numpy(self, query_components, query_values, doc_ids_per_query, k, device):
         scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
         out = []
@@ -400,6 +424,7 @@ class _IndexBase(_ScoreMixin):
         self._doc_ids = doc_ids
         self._contents = contents
         self._doc_pos = None
+        self._tokens = None   # component -> token (batch_explain)
         self._device = device
         self._uploaded = False
         if upload:
@@ -608,6 +633,11 @@ class _IndexBase(_ScoreMixin):
     def _score_name(self, row):
         return self._doc_ids[row]
 
+    def _score_token(self, component):
+        if self._tokens is None:
+            self._tokens = {i: t for t, i in self._tm.items()}
+        return self._tokens[component]
+
     # ---- search -------------------------------------------------------
     def _remap(self, query_id, sc, ids, n):
         n, q, names = int(n), str(query_id), self._doc_ids
@@ -774,6 +804,9 @@ class _RawBase(_ScoreMixin):
 
     def _score_name(self, row):
         return row
+
+    def _score_token(self, component):
+        return component
 
     def search(self, query_components, query_values, k, query_cut, heap_factor, n_knn, sorted, filter=None):
         """-> [(score, doc_id)] (reference src/pylib/mod.rs:1033-1076). filter: a SeismicFilter of this index or an
