@@ -32,6 +32,22 @@ sgpu_status sgpu_debug_plan(const sgpu_index* idx, const uint64_t* q_off, const 
 /* the same plan as the DEVICE computes it for staged chunks (needs an uploaded index; 1 ... 16384 queries, query_cut 1 ... 16) */
 sgpu_status sgpu_debug_device_plan(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
                                    uint32_t nq, uint32_t query_cut, uint32_t* order_out, uint32_t* out3);
+/* the launch configuration of a search pass, as the library's pure function decides it; needs no index and no device. The
+ * SGPU_* names are read from the environment as a launch reads them. n_in must be 23, n_out 58.
+ * in:  [0] n_cu [1] LDS bytes per workgroup [2] comp_width [3] value_type [4] dim [5] val_scale (float bits)
+ *      [6] cooperative variant switched off for the replica [7] nq [8] longest query [9] k_max [10] staged batch
+ *      [11] 1 = a launch plan follows / 0 = none [12] block dots a query needs at most [13] largest first list
+ *      [14] largest list [15] every query has a hash seed [16] MODE_DOTS: blocks of the target list
+ *      [17] k [18] query_cut [19] n_knn [20] first_sorted [21] mode (0 search, 1 dots, 2 counted)
+ *      [22] workgroups the occupancy query allows, n_cu x workgroups per CU (0: no grid wanted)
+ * out: [0..19] the LDS layout: byte offsets q_comp q_val q_sc q_bits q_rank sel rt_start rt_mid rt_pre dots order uni part
+ *      heap st, then qc qn qg dots_cap total  [20..33] the kernel parameters: k query_cut heap_factor first_sorted mode
+ *      items_max items_init items_min rblocks_max n_knn target_list val_scale queue_base ring
+ *      [34] lookup [35] workgroup size [36] LDS bytes [37] counted [38] streamed [39] ring [40] cooperative: 0 / 1 / 2 forced
+ *      [41..49] max_pos max_cand chunk chunk_min min_items first_reach idle_min idle_ratio poll_sleep
+ *      [50] most workgroups of an unforced cooperative launch (0: every slot) [51] grid [52] cooperative grid before the
+ *      board's 512 slots cap it [53..57] the board's byte offsets: slots pos cand trace total */
+sgpu_status sgpu_debug_launch_config(const uint32_t* in, uint32_t n_in, float heap_factor, uint32_t* out, uint32_t n_out);
 /* the calling thread's staged calls add their host-side phase times to buf8[0..7] from now on (NULL: off) */
 void sgpu_debug_call_timing(double* buf8);
 /* timeline of the last cooperative launch (trace builds) */

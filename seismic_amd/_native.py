@@ -140,6 +140,33 @@ def device_count():
     return n.value if st == SGPU_OK else 0
 
 
+# sgpu_debug_launch_config (include/seismic_hip_testing.h): the words it takes, with the values of an MI355X and of a
+# launch nobody described further, and the words it returns
+LAUNCH_CONFIG_IN = dict(n_cu=256, max_lds=160 * 1024, comp_width=2, value_type=0, dim=30522, val_scale_bits=0, coop_broken=0,
+                        nq=1, max_nnz=32, k_max=1024, staged=0, has_plan=1, dots_cap=1, max_nb=0, max_list_nb=1, hash_ok=0,
+                        target_list_nb=0, k=10, query_cut=4, n_knn=0, first_sorted=0, mode=0, occupancy_grid=0)
+LAUNCH_CONFIG_OUT = ("q_comp q_val q_sc q_bits q_rank sel rt_start rt_mid rt_pre dots order uni part heap st qc qn qg dots_cap total "
+                     "p_k p_query_cut p_heap_factor_bits p_first_sorted p_mode items_max items_init items_min rblocks_max p_n_knn "
+                     "target_list p_val_scale_bits queue_base p_ring "
+                     "lookup block lds_bytes counted streamed ring coop max_pos max_cand chunk chunk_min min_items first_reach "
+                     "idle_min idle_ratio poll_sleep coop_grid grid grid_uncapped board_slots board_pos board_cand board_trace "
+                     "board_total").split()
+
+
+def debug_launch_config(heap_factor=1.0, **fields):
+    """The launch configuration the library would choose (test hook, no device): fields override LAUNCH_CONFIG_IN, the
+    SGPU_* knobs are read from the environment. Returns the output words by name; SeismicHipError where a launch fails."""
+    unknown = set(fields) - set(LAUNCH_CONFIG_IN)
+    if unknown:
+        raise TypeError("unknown launch fact(s): %s" % ", ".join(sorted(unknown)))
+    w = np.array([int(fields.get(name, dflt)) for name, dflt in LAUNCH_CONFIG_IN.items()], np.uint32)
+    out = np.zeros(len(LAUNCH_CONFIG_OUT), np.uint32)
+    fn = lib().sgpu_debug_launch_config
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32]
+    check(fn(_p(w), len(w), float(heap_factor), _p(out), len(out)))
+    return dict(zip(LAUNCH_CONFIG_OUT, (int(x) for x in out)))
+
+
 def params(k, query_cut, heap_factor, first_sorted, n_knn=0):
     return SearchParams(k=int(k), query_cut=int(query_cut), heap_factor=float(heap_factor),
                         n_knn=int(n_knn), first_sorted=1 if first_sorted else 0)

@@ -13,7 +13,7 @@
 struct sgpu_batch;
 
 namespace sgpu {
-// device_index.hip
+// device_index.hip (residency, lanes), launch_plan.hip, batch.hip, staged.hip
 struct Lane;
 sgpu_status device_index_upload(const HostIndex& h, int device, DeviceIndex** out);
 sgpu_status device_index_clone(const DeviceIndex* src, int device, DeviceIndex** out);
@@ -54,6 +54,8 @@ uint32_t debug_lane_chunk(DeviceIndex* d, uint32_t lane, uint32_t* info4, uint32
 const DeviceIndex* batch_replica(const sgpu_batch* b);
 sgpu_status device_index_set_knn(DeviceIndex* d, const std::vector<uint32_t>& knn, uint32_t knn_dim);
 sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);
+// launch_config.cpp
+sgpu_status debug_launch_config(const uint32_t* in, uint32_t n_in, float heap_factor, uint32_t* out, uint32_t n_out);
 // exact_device.hip
 sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
@@ -385,7 +387,7 @@ static uint32_t call_segments(uint32_t nq) {
 // that chunk i's tail leaves idle. Who plans which chunk: chunk 0 goes out unplanned where the device could plan it (input
 // order, no kernel ahead of its search), every later chunk is planned HERE, on the calling thread, after the chunk before
 // it has been enqueued - the thread would only wait, and the chunk's search is then queued and ready long before the
-// previous search's workgroups start to leave (staged_launch, device_index.hip); a call that is one launch keeps the
+// previous search's workgroups start to leave (staged_launch, staged.hip); a call that is one launch keeps the
 // device plan.
 // (flt: the filter of a filtered call and the replica d is, or null; [s0, s1): the queries of the caller's arrays this
 // segment serves - offsets, rows and error messages stay the whole shard's)
@@ -722,7 +724,7 @@ uint32_t sgpu_debug_call_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_
 }
 
 // (the last chunk pool lane `lane` of replica 0 served: who planned it and, host-planned, the order it went down with -
-// device_index.hip debug_lane_chunk; tests/test_gpu_entry_chunks.py)
+// staged.hip debug_lane_chunk; tests/test_gpu_entry_chunks.py)
 uint32_t sgpu_debug_lane_chunk(sgpu_index* idx, uint32_t lane, uint32_t* info4, uint32_t* order_out, uint32_t cap) {
   SGPU_HOOK_OR(0u);
   if (!idx || !idx->dev || !info4) return 0u;
@@ -791,8 +793,16 @@ sgpu_status sgpu_debug_device_plan(sgpu_index* idx, const uint64_t* q_off, const
   return debug_device_plan(idx->dev, q_off, comps, vals, nq, query_cut, order_out, out3);
 }
 
+// (not part of the boundary: the launch configuration - launch_config.cpp - of a launch described by 23 words and
+// heap_factor, as 58 words; the knobs come from the environment as a launch reads them. Needs no index and no device)
+sgpu_status sgpu_debug_launch_config(const uint32_t* in, uint32_t n_in, float heap_factor, uint32_t* out, uint32_t n_out) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!in || !out) return fail(SGPU_EINVAL, "null argument");
+  return debug_launch_config(in, n_in, heap_factor, out, n_out);
+}
+
 // (not part of the boundary: the calling thread's staged calls add the wall time of their host-side phases to
-// buf[0..7] from now on - see device_index.hip: call_timing; null switches it off. tools/shard_probe.py)
+// buf[0..7] from now on - see staged.hip: call_timing; null switches it off. tools/shard_probe.py)
 void sgpu_debug_call_timing(double* buf8) {
   SGPU_HOOK_OR();
   call_timing() = buf8;

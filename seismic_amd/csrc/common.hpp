@@ -25,8 +25,10 @@ bool test_hooks_on();
 int default_host_threads(int omp_max_threads);
 
 // The largest launch one chunk of an entry-point call becomes (abi.cpp: a call is cut so that no chunk exceeds it) = the
-// largest launch the device plans (device_types.hpp: kDevicePlanMaxQueries, which device_index.hip checks against this).
+// largest launch the device plans (device_types.hpp: kDevicePlanMaxQueries, which launch_plan.hip checks against this).
 constexpr uint32_t kChunkQueriesMax = 16384;
+
+inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }   // device arrays start on multiples of 16 bytes
 }  // namespace sgpu
 #ifdef _OPENMP
 #include <omp.h>

@@ -2,7 +2,7 @@
 //
 // The search kernel wants two things per launch that depend on the queries: the processing order (longest expected
 // query first: the a-priori cost is the postings of the lists a query will walk) and, for the LDS layout, the largest
-// number of block dots a query needs. Until r05 the host computed both (make_plan, device_index.hip: ~0.2 us per query,
+// number of block dots a query needs. Until r05 the host computed both (make_plan, launch_plan.hip: ~0.2 us per query,
 // serial on the calling thread: 2.2 ms of a 10 000-query sgpu_batch_search call next to a 5.7 ms kernel; VERDICT r05
 // "one call, one thread, full rate"). The reference's batch_search is ONE call whose per-query cost does not depend on
 // who calls it (src/pylib/mod.rs:1111-1146); here the plan moves behind the H2D copy of the queries:

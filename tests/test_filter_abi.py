@@ -266,7 +266,16 @@ def test_the_posting_view_hook_is_a_test_hook(monkeypatch):
         for filt in (None, f.h, fo.h):
             st, sizes = call(filt)
             assert st == SGPU_EINVAL and "test hook" in _err() and (sizes == 77).all()
+        # (sgpu_debug_launch_config, the other hook that needs no device, obeys the same switch)
+        words, cfg = np.array(list(_native.LAUNCH_CONFIG_IN.values()), np.uint32), np.full(len(_native.LAUNCH_CONFIG_OUT), 77, np.uint32)
+        L.sgpu_debug_launch_config.argtypes = [vp, ctypes.c_uint32, ctypes.c_float, vp, ctypes.c_uint32]
+        assert L.sgpu_debug_launch_config(p(words), len(words), 1.0, p(cfg), len(cfg)) == SGPU_EINVAL
+        assert "sgpu_debug_launch_config is a test hook" in _err() and (cfg == 77).all()
     monkeypatch.setenv("SGPU_TEST_HOOKS", "1")
+    assert L.sgpu_debug_launch_config(p(words), len(words), 1.0, p(cfg), len(cfg)) == 0 and cfg[35] in (512, 1024)
+    header = open(os.path.join(ROOT, "include", "seismic_hip_testing.h")).read()
+    assert re.search(r"\bsgpu_debug_launch_config\s*\(", header)
+    assert "sgpu_debug_launch_config" not in open(os.path.join(ROOT, "include", "seismic_hip.h")).read()
     for filt in (None, f.h):
         st, _ = call(filt)
         assert st == SGPU_EDEVICE and "upload" in _err()

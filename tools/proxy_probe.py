@@ -2,7 +2,7 @@
 """What predicts a query's time in the search kernel? Dumps, per query of the 8.8M-document shape, the kernel's own
 clocks and work counters (profiling build) next to what the host knows BEFORE the launch (postings / blocks / weights of the
 lists the query will walk, its length), once inside a 10 000-query launch and once inside 1250-query launches.
-The launch plan orders queries by an a-priori cost (make_plan in device_index.hip); this is the data that cost is fitted on.
+The launch plan orders queries by an a-priori cost (make_plan in launch_plan.hip); this is the data that cost is fitted on.
 usage: proxy_probe.py OUT.npz [--docs N]"""
 import os
 os.environ.setdefault("SGPU_TEST_HOOKS", "1")   # (the SGPU_* knobs and sgpu_debug_* entry points this tool drives are test hooks)
