@@ -493,6 +493,46 @@ sgpu_status sgpu_explain_documents_host(const sgpu_index* idx,
     float* out_scores, uint32_t* out_n_terms,
     uint32_t* out_comps, float* out_q_vals, float* out_d_vals, float* out_products);
 
+/* ---- expand: Rocchio feedback queries ------------------------------------------
+ * Pseudo-relevance feedback in one call: fold the vectors of a query's feedback documents (usually the best of a first
+ * search) into the query, keep the heaviest terms, search again with the row that comes back. The reference has no
+ * counterpart. Queries and candidates are given exactly as for sgpu_score_documents (any order, repeats allowed, possibly
+ * none); cand_w[i] is the weight of feedback document cand_ids[i] - the caller forms beta / |R|, or a weight that depends
+ * on the score; weights may be negative.
+ * The table. For query q define the dense f32 vector W over the vocabulary: W starts at +0.0 everywhere. For each query
+ * element (c, w), in the order given, W[c] = fl(alpha * w) (set, not added). Then for each candidate i of q IN THE ORDER
+ * GIVEN, for each stored element e < len(d) of its document d with component c: W[c] = fl(W[c] + p), where p is the
+ * product rule of sgpu_explain_documents with cand_w[i] in the place of the query weight - F16: fl(cand_w[i] * f32(value));
+ * FIXEDU8 and DOTVBYTE: fl(fl(cand_w[i] * val_scale) * (float)code), with the same narrowing (a cand_w[i] * val_scale
+ * that underflows is outside this contract). Multiply then add, never contracted. A document's components are distinct,
+ * so the additions of one document do not depend on each other: the only order that matters is the order of the
+ * documents, and it is fixed. A document listed twice is added twice. Padding elements of a record add nothing.
+ * Which terms are returned. The terms of q are the components with W[c] > 0 (pairs whose W holds a NaN or an inf are
+ * outside this contract). The t best are kept, by (W descending, component ascending); out_n[q] = min(t, terms of q).
+ * Row q of the nq x t row-major out_comps / out_vals holds the kept terms in ASCENDING COMPONENT ORDER, slots past
+ * out_n[q] are zero: the first out_n[q] entries of a row are a valid query for sgpu_batch_search as they stand.
+ * Checks, in this order: null arguments (SGPU_EINVAL; cand_ids, cand_w and the three outputs too, also when there is
+ * nothing to do), everything sgpu_score_documents checks in its order, an alpha or a cand_w[i] that is not finite
+ * (SGPU_EINVAL; the message names the first such candidate and its query), a query of more than 65536 candidates
+ * (SGPU_ELIMIT), t == 0 (SGPU_EINVAL), t > 1024 (SGPU_ELIMIT), index not uploaded or replica out of range (SGPU_EDEVICE),
+ * device memory (SGPU_ENOMEM; the index stays usable). nq == 0 is SGPU_OK.
+ * The call shares the score calls' per-replica stream, mutex and recycled scratch and takes turns with them; it is safe
+ * beside searches, filtered and exact calls. It adds no index array; its scratch is freed by sgpu_index_destroy or a new
+ * upload. A launch takes whole queries only: SGPU_SCORE_CHUNK (candidates per launch, default 2^20) cuts between
+ * queries, a query of more candidates than that goes alone; the outputs do not depend on the cuts. */
+sgpu_status sgpu_expand_queries(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w,
+    float alpha, uint32_t t,
+    uint32_t* out_comps, float* out_vals, uint32_t* out_n);
+/* The same on the host cores (needs no upload): the arbiter of the contract above, the device call returns its bits;
+ * the same checks without the device ones. num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_expand_queries_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w,
+    float alpha, uint32_t t, uint32_t num_threads,
+    uint32_t* out_comps, float* out_vals, uint32_t* out_n);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

@@ -57,6 +57,10 @@ uint32_t sgpu_debug_coop_trace(sgpu_index* idx, uint64_t* out, uint32_t cap);
  * the selection kernels (0 for a score call), merge rounds the selection ran after its chunk round, summed over the
  * call's launches}; SGPU_EINVAL before the first call */
 sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* out8);
+/* what the last sgpu_expand_queries call on `replica` measured: out8 = {device ms of its kernels (HIP events), launches,
+ * 1 = the table in LDS / 0 = in global memory, grid of its last launch, workgroup size, LDS bytes, bytes of the global
+ * tables (0 with the table in LDS), 0}; SGPU_EINVAL before the replica's first score or expand call */
+sgpu_status sgpu_debug_expand_stats(sgpu_index* idx, uint32_t replica, double* out8);
 /* the accumulate launches of the last sgpu_exact_search_device[_filtered] call on `replica`: one per chunk of queries whose
  * candidates (n_ranges x k x 8 bytes per query) fit the candidate buffer of 256 MiB; the environment name
  * SGPU_EXACT_CAND_BYTES, read per call and honoured under the same switch, lowers that size. SGPU_EINVAL before the

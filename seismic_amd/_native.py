@@ -92,6 +92,9 @@ def lib():
         L.sgpu_rerank_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.sgpu_explain_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32] + [vp] * 6
         L.sgpu_explain_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32] + [vp] * 6
+        L.sgpu_expand_queries.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32, vp, vp, vp]
+        L.sgpu_expand_queries_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32, C.c_uint32, vp, vp,
+                                               vp]
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -498,6 +501,52 @@ class NativeIndex:
         check(lib().sgpu_explain_documents_host(self.h, _p(q_off), _p(comps), _p(vals), len(q_off) - 1, _p(cand_off), _p(cand),
                                                 m, int(num_threads), *[_p(a) for a in out]))
         return tuple(a[:n] for a in out)
+
+    # ---- Rocchio feedback queries ----
+    @staticmethod
+    def _expand_buffers(q_off, comps, vals, cand_off, cand_ids, cand_w, t):
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        cand_w = np.ascontiguousarray(cand_w, np.float32)
+        if len(cand_w) != len(cand_ids):
+            raise ValueError("%d candidates but %d weights" % (len(cand_ids), len(cand_w)))
+        nq, t = len(q_off) - 1, int(t)
+        if not 0 <= t < 2 ** 32:
+            raise ValueError("t = %d" % t)
+        rows = (max(nq, 1), t if 1 <= t <= 1024 else 1)   # (a t the library refuses: nothing is written)
+        oc, ov, n = np.zeros(rows, np.uint32), np.zeros(rows, np.float32), np.zeros(max(nq, 1), np.uint32)
+        if not len(cand_ids):
+            cand_ids, cand_w = np.zeros(1, np.uint64), np.zeros(1, np.float32)
+        return q_off, comps, vals, cand_off, cand_ids, cand_w, nq, t, oc, ov, n
+
+    def expand_queries(self, q_off, comps, vals, cand_off, cand_ids, cand_w, alpha, t, replica=0):
+        """sgpu_expand_queries: per query the Rocchio table W = alpha * query + sum of cand_w[i] * document cand_ids[i] (the
+        documents added in the order given, f32, see include/seismic_hip.h), its t <= 1024 heaviest components with
+        W > 0 (ties: the smaller component) in ascending component order, built on the device of `replica`. Returns
+        (components u32 [nq, t], values f32 [nq, t], n u32 [nq]); slots past n[q] are zero."""
+        q_off, comps, vals, cand_off, cand, w, nq, t, oc, ov, n = self._expand_buffers(q_off, comps, vals, cand_off, cand_ids,
+                                                                                      cand_w, t)
+        check(lib().sgpu_expand_queries(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), _p(w),
+                                        float(alpha), t, _p(oc), _p(ov), _p(n)))
+        return oc[:nq], ov[:nq], n[:nq]
+
+    def expand_queries_host(self, q_off, comps, vals, cand_off, cand_ids, cand_w, alpha, t, num_threads=0):
+        """sgpu_expand_queries_host: the same rows on the host cores (needs no upload), bit-identical."""
+        q_off, comps, vals, cand_off, cand, w, nq, t, oc, ov, n = self._expand_buffers(q_off, comps, vals, cand_off, cand_ids,
+                                                                                      cand_w, t)
+        check(lib().sgpu_expand_queries_host(self.h, _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), _p(w),
+                                             float(alpha), t, int(num_threads), _p(oc), _p(ov), _p(n)))
+        return oc[:nq], ov[:nq], n[:nq]
+
+    def debug_expand_stats(self, replica=0):
+        """sgpu_debug_expand_stats (test hook): what the last expand_queries call on `replica` measured."""
+        out = np.zeros(8, np.float64)
+        fn = lib().sgpu_debug_expand_stats
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        check(fn(self.h, int(replica), _p(out)))
+        return dict(kernel_ms=float(out[0]), launches=int(out[1]), dense=int(out[2]), grid=int(out[3]), block=int(out[4]),
+                    lds=int(out[5]), table_bytes=int(out[6]))
 
 
 def _filter_handle(f):

@@ -72,6 +72,10 @@ sgpu_status explain_documents_device(sgpu_index* idx, uint32_t replica, const ui
                                      const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
                                      const ExplainOut& out);
 bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
+                                  uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
+bool expand_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
 const sgpu_index* filter_index(const sgpu_filter* f);
@@ -896,6 +900,31 @@ sgpu_status sgpu_explain_documents_host(const sgpu_index* idx, const uint64_t* q
   if (!idx) return fail(SGPU_EINVAL, "null argument");
   const ExplainOut out{out_scores, out_n_terms, out_comps, out_q_vals, out_d_vals, out_products};
   return explain_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, m, num_threads, out);
+}
+
+sgpu_status sgpu_expand_queries(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
+                                uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n) {
+  return expand_queries_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha, t, out_comps, out_vals, out_n);
+}
+
+sgpu_status sgpu_expand_queries_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                     uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w,
+                                     float alpha, uint32_t t, uint32_t num_threads, uint32_t* out_comps, float* out_vals,
+                                     uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  return expand_queries_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha, t, num_threads, out_comps,
+                             out_vals, out_n);
+}
+
+// (not part of the boundary: what the last sgpu_expand_queries call on `replica` measured - out8 = {device ms of its kernels,
+// launches, 1 = table in LDS / 0 = in global memory, grid of the last launch, workgroup size, LDS bytes, bytes of the
+// global tables, 0}; SGPU_EINVAL before the replica's first score or expand call. tools/expand_probe.py)
+sgpu_status sgpu_debug_expand_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");
+  if (!expand_debug_stats(idx, replica, out8)) return fail(SGPU_EINVAL, "no expand call has run on replica %u", replica);
+  return SGPU_OK;
 }
 
 // (not part of the boundary: what the last sgpu_score_documents / sgpu_rerank_documents / sgpu_explain_documents call on `replica` measured - out8 =

@@ -124,6 +124,15 @@ sgpu_status explain_check_args(const HostIndex& h, const uint64_t* q_off, const 
 sgpu_status explain_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, uint32_t num_threads,
                                    const ExplainOut& out);
+// Rocchio feedback queries (sgpu_expand_queries_host) and checks 1 - 6 both expand calls run
+constexpr uint32_t kExpandMaxTerms = 1024;
+constexpr uint64_t kExpandMaxCand = 65536;   // feedback documents of one query
+sgpu_status expand_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                              const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha, uint32_t t,
+                              const uint32_t* out_comps, const float* out_vals, const uint32_t* out_n, uint32_t* max_nnz);
+sgpu_status expand_queries_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha, uint32_t t,
+                                uint32_t num_threads, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
 // score_documents.hip
 void score_state_free(ScoreState* s);
 

@@ -46,6 +46,10 @@
 // sgpu_explain_documents runs through the same launcher (score_run: the staged queries, the tiles, the cuts into launches,
 // the per-replica stream, mutex and scratch) with explain_documents.hip's kernel in score_documents_kernel's place; what
 // the two kernels share is score_lookup.hpp.
+//
+// sgpu_expand_queries has a launcher of its own, expand_run, because its unit of work is a whole query and not a tile of
+// candidates: it cuts between queries only. It shares ScoreState with score_run - the stream, the mutex, the staged
+// queries and ids - and adds the buffers its rows and tables need; the kernel is expand_queries.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -313,6 +317,9 @@ struct ScoreState {
   // rerank: a launch's selection tasks and k-key slots, the two carry slots, the call's rows (scores, ids, counts)
   DeviceBuffer sel_tasks, slots, carry, row_scores, row_ids, row_n;
   DeviceBuffer terms;   // explain: a launch's term counts and its four arrays of rows
+  // expand: the call's candidate offsets and rows (components, values, counts), a launch's candidate weights and, where
+  // the table does not fit LDS, one table per workgroup
+  DeviceBuffer x_cand_off, x_comps, x_vals, x_n, x_w, x_table;
   std::vector<uint4> h_tiles;   // host staging of a launch
   std::vector<uint32_t> h_ids;
   std::vector<std::vector<SelTask>> sel_rounds;   // [round * tiers + tier]
@@ -321,6 +328,9 @@ struct ScoreState {
   uint32_t last_merge_rounds = 0;
   double last_kernel_ms = 0;    // device time of the last call's kernels, its launches and its lookup form (sgpu_debug_score_stats)
   uint32_t last_launches = 0, last_dense = 0, last_grid = 0, last_block = 0, last_lds = 0;
+  double x_kernel_ms = 0;       // the same of the last expand call (sgpu_debug_expand_stats)
+  uint32_t x_launches = 0, x_dense = 0, x_grid = 0, x_lds = 0;
+  uint64_t x_table_bytes = 0;
 };
 
 void score_state_free(ScoreState* s) {
@@ -328,7 +338,8 @@ void score_state_free(ScoreState* s) {
   if (s->device >= 0) (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (DeviceBuffer* b : {&s->q_off, &s->q_comp, &s->q_val, &s->tiles, &s->cand, &s->scores, &s->sel_tasks, &s->slots, &s->carry,
-                          &s->row_scores, &s->row_ids, &s->row_n, &s->terms})
+                          &s->row_scores, &s->row_ids, &s->row_n, &s->terms, &s->x_cand_off, &s->x_comps, &s->x_vals, &s->x_n,
+                          &s->x_w, &s->x_table})
     b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -737,6 +748,149 @@ sgpu_status explain_documents_device(sgpu_index* idx, uint32_t replica, const ui
   } catch (const std::bad_alloc&) {
     return fail(SGPU_ENOMEM, "out of host memory");
   }
+}
+
+// ---- sgpu_expand_queries ----
+constexpr uint64_t kExpandTableBytes = 1ull << 30;   // most global scratch the tables of a launch's workgroups take
+
+// An expand call: expand_queries.hip's kernel over the call's queries, staged as score_run stages them. A launch takes
+// whole queries - consecutive ones while their candidates fit the budget (SGPU_SCORE_CHUNK), a larger query alone -, so
+// no table is carried between launches; the call's rows stay on the device until its end.
+static sgpu_status expand_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
+                              const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w,
+                              float alpha, uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n) {
+  HIP_TRY(hipSetDevice(s->device));
+  s->x_kernel_ms = 0;
+  s->x_launches = 0;
+  // the table: in LDS where the vocabulary fits (the score kernel's rule for its dense table; test hook
+  // SGPU_SCORE_LOOKUP=2: in global memory although it fits), else one per workgroup in the scratch
+  const uint64_t table_bytes = ((h.dim + 1) * 4 + 15) & ~15ull;
+  bool dense = table_bytes <= kScoreDenseLds;
+  if (test_hooks_on()) {
+    const char* v = std::getenv("SGPU_SCORE_LOOKUP");
+    if (v && *v == '2') dense = false;
+  }
+  const uint32_t lds = dense ? (uint32_t)table_bytes : 0u;
+  int per_cu = 0;
+  sgpu_status st;
+  if ((st = expand_kernel_fit(h.comp_width, h.value_type, dense, lds, &per_cu)) != SGPU_OK) return st;
+  if (per_cu < 1) return fail(SGPU_ELIMIT, "the expand kernel does not fit on a CU (%u bytes of LDS)", lds);
+  per_cu = std::min(per_cu, (int)(2048u / kExpandBlock));
+  uint64_t max_grid = (uint64_t)s->n_cu * (uint32_t)per_cu;
+  if (!dense) max_grid = std::max<uint64_t>(1, std::min<uint64_t>(max_grid, kExpandTableBytes / ((h.dim + 1) * 4)));
+  if (test_hooks_on())   // (test hook SGPU_EXPAND_GRID: fewer workgroups, so that each takes many queries in turn)
+    if (const char* v = std::getenv("SGPU_EXPAND_GRID"))
+      if (*v) max_grid = std::max<uint64_t>(1, std::min<uint64_t>(max_grid, std::strtoull(v, nullptr, 10)));
+
+  uint64_t budget = kScoreChunk;
+  if (const char* v = std::getenv("SGPU_SCORE_CHUNK"))
+    if (*v) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  budget = std::min<uint64_t>(budget, 1ull << 28);
+
+  const uint64_t qnnz = q_off[nq], cells = (uint64_t)nq * t;
+  if ((st = score_reserve(s, s->q_off, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = score_reserve(s, s->q_comp, qnnz * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->q_val, qnnz * 4)) != SGPU_OK || (st = score_reserve(s, s->x_cand_off, (uint64_t)(nq + 1) * 8)) != SGPU_OK ||
+      (st = score_reserve(s, s->x_comps, cells * 4)) != SGPU_OK || (st = score_reserve(s, s->x_vals, cells * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->x_n, (uint64_t)nq * 4)) != SGPU_OK)
+    return st;
+  HIP_TRY(hipMemcpyAsync(s->q_off.p, q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->x_cand_off.p, cand_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, s->stream));
+  if (qnnz) {
+    HIP_TRY(hipMemcpyAsync(s->q_comp.p, comps, qnnz * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->q_val.p, vals, qnnz * 4, hipMemcpyHostToDevice, s->stream));
+  }
+  ExpandArgs a{};
+  a.fwd = view.fwd;
+  a.doc_ref = view.doc_ref;
+  a.q_off = s->q_off.as<const uint64_t>();
+  a.q_comp = s->q_comp.as<const uint32_t>();
+  a.q_val = s->q_val.as<const float>();
+  a.cand_off = s->x_cand_off.as<const uint64_t>();
+  a.out_comps = s->x_comps.as<uint32_t>();
+  a.out_vals = s->x_vals.as<float>();
+  a.out_n = s->x_n.as<uint32_t>();
+  a.dim = (uint32_t)h.dim;
+  a.t = t;
+  a.alpha = alpha;
+  a.val_scale = h.val_scale;
+  s->x_dense = dense;
+  s->x_lds = lds;
+  s->x_table_bytes = 0;
+
+  for (uint32_t q = 0; q < nq;) {
+    const uint32_t qa = q;
+    const uint64_t first = cand_off[qa];
+    ++q;   // (a query of more candidates than the budget goes alone)
+    while (q < nq && cand_off[q + 1] - first <= budget) ++q;
+    const uint64_t n_cand = cand_off[q] - first;   // (<= max(budget, kExpandMaxCand) < 2^32)
+    s->h_ids.resize(n_cand);
+    for (uint64_t i = 0; i < n_cand; ++i) s->h_ids[i] = (uint32_t)cand_ids[first + i];
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(q - qa, max_grid);
+    if ((st = score_reserve(s, s->cand, n_cand * 4)) != SGPU_OK || (st = score_reserve(s, s->x_w, n_cand * 4)) != SGPU_OK) return st;
+    if (!dense) {
+      const uint64_t bytes = (uint64_t)grid * (h.dim + 1) * 4;
+      if ((st = score_reserve(s, s->x_table, bytes)) != SGPU_OK) return st;
+      s->x_table_bytes = std::max(s->x_table_bytes, bytes);
+    }
+    if (n_cand) {
+      HIP_TRY(hipMemcpyAsync(s->cand.p, s->h_ids.data(), n_cand * 4, hipMemcpyHostToDevice, s->stream));
+      HIP_TRY(hipMemcpyAsync(s->x_w.p, cand_w + first, n_cand * 4, hipMemcpyHostToDevice, s->stream));
+    }
+    a.cand = s->cand.as<const uint32_t>();
+    a.cand_w = s->x_w.as<const float>();
+    a.table = s->x_table.as<float>();
+    a.cand_base = first;
+    a.q_first = qa;
+    a.q_last = q;
+    s->x_grid = grid;
+    HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    if ((st = expand_kernel_launch(h.comp_width, h.value_type, dense, grid, lds, s->stream, a)) != SGPU_OK) return st;
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (the staged ids and the scratch are the next launch's)
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->x_kernel_ms += ms;
+    s->x_launches += 1;
+  }
+  HIP_TRY(hipMemcpyAsync(out_comps, s->x_comps.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_vals, s->x_vals.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_n, s->x_n.p, (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SGPU_OK;
+}
+
+sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
+                                  uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  uint32_t max_nnz = 0;
+  const sgpu_status vst =
+      expand_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha, t, out_comps, out_vals, out_n, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  ScoreState* s = nullptr;
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
+  if (nq == 0) return SGPU_OK;
+  std::lock_guard<std::mutex> lk(s->mu);
+  try {
+    return expand_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha,
+                      t, out_comps, out_vals, out_n);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+// (test hook: what the last expand call on `replica` measured - out8 = {device ms of its kernels, launches, 1 = table in LDS /
+// 0 = in global memory, grid of the last launch, workgroup size, LDS bytes, bytes of the global tables, 0}. tools/expand_probe.py)
+bool expand_debug_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  std::lock_guard<std::mutex> lk(idx->score_mu);
+  if (replica >= idx->score.size() || !idx->score[replica]) return false;
+  ScoreState* s = idx->score[replica];
+  std::lock_guard<std::mutex> lk2(s->mu);
+  const double v[8] = {s->x_kernel_ms, (double)s->x_launches, (double)s->x_dense, (double)s->x_grid,
+                       (double)kExpandBlock, (double)s->x_lds, (double)s->x_table_bytes, 0.0};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
+  return true;
 }
 
 // (test hook: what the last score or rerank call on `replica` measured - out8 = {device ms of its score kernels, launches,

@@ -1,5 +1,5 @@
-// score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host and sgpu_explain_documents_host, and the
-// argument checks they share with the device calls.
+// score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host, sgpu_explain_documents_host and
+// sgpu_expand_queries_host, and the argument checks they share with the device calls.
 //
 // The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
@@ -279,6 +279,120 @@ sgpu_status explain_documents_host(const HostIndex& h, const uint64_t* q_off, co
       }
     }
     for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+  }
+  return SGPU_OK;
+}
+
+// Checks 1 - 6 of sgpu_expand_queries, in the header's order.
+sgpu_status expand_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                              const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha, uint32_t t,
+                              const uint32_t* out_comps, const float* out_vals, const uint32_t* out_n, uint32_t* max_nnz) {
+  if (!cand_w || !out_comps || !out_n) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out_vals, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (!std::isfinite(alpha)) return fail(SGPU_EINVAL, "alpha is not finite");
+  for (uint32_t q = 0; q < nq; ++q)
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i)
+      if (!std::isfinite(cand_w[i]))
+        return fail(SGPU_EINVAL, "query %u: the weight of candidate %llu (document id %llu) is not finite", q,
+                    (unsigned long long)(i - cand_off[q]), (unsigned long long)cand_ids[i]);
+  for (uint32_t q = 0; q < nq; ++q)
+    if (cand_off[q + 1] - cand_off[q] > kExpandMaxCand)
+      return fail(SGPU_ELIMIT, "query %u has %llu feedback documents (expanding queries: limit %llu)", q,
+                  (unsigned long long)(cand_off[q + 1] - cand_off[q]), (unsigned long long)kExpandMaxCand);
+  if (t == 0) return fail(SGPU_EINVAL, "t must be at least 1");
+  if (t > kExpandMaxTerms) return fail(SGPU_ELIMIT, "t = %u (expanding queries: limit %u)", t, kExpandMaxTerms);
+  return SGPU_OK;
+}
+
+// The host twin of expand_queries.hip, the arbiter of its rows: per query the table W of the header - the query's
+// fl(alpha * w) written, then every feedback document added in the order given, multiply then add -, the components with
+// W > 0 cut to the t best by (W descending, component ascending) and written in ascending component order. A thread keeps
+// one table over the vocabulary and the list of the components it touched, each once (`seen`), so that a query costs
+// its own elements and not the vocabulary.
+sgpu_status expand_queries_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha, uint32_t t,
+                                uint32_t num_threads, uint32_t* out_comps, float* out_vals, uint32_t* out_n) {
+  uint32_t max_nnz = 0;
+  const sgpu_status vst =
+      expand_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha, t, out_comps, out_vals, out_n, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  struct Scratch {
+    std::vector<float> w;
+    std::vector<uint8_t> seen;
+    std::vector<uint32_t> touched;
+  };
+  std::vector<Scratch> scratch;
+  try {
+    scratch.assign((size_t)team, Scratch());
+    for (auto& s : scratch) {
+      s.w.assign(h.dim, 0.0f);
+      s.seen.assign(h.dim, 0);
+      s.touched.reserve(h.dim);   // (a component enters once: nothing below allocates)
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 16) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+#ifdef _OPENMP
+    Scratch& s = scratch[(size_t)omp_get_thread_num()];
+#else
+    Scratch& s = scratch[0];
+#endif
+    float* W = s.w.data();
+    uint8_t* seen = s.seen.data();
+    std::vector<uint32_t>& touched = s.touched;
+    touched.clear();
+    auto touch = [&](uint32_t c) {
+      if (!seen[c]) {
+        seen[c] = 1;
+        touched.push_back(c);
+      }
+    };
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) {
+      touch(comps[j]);
+      W[comps[j]] = alpha * vals[j];
+    }
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
+      const uint64_t a = h.fwd_offsets[cand_ids[i]], e = h.fwd_offsets[cand_ids[i] + 1];
+      const float wd = f16 ? cand_w[i] : cand_w[i] * h.val_scale;
+      for (uint64_t x = a; x < e; ++x) {
+        const uint32_t c = h.comp(x);
+        const float p = wd * (f16 ? f16_to_f32(h.fwd_vals[x]) : (float)h.fwd_codes[x]);
+        touch(c);
+        W[c] = W[c] + p;
+      }
+    }
+    // the terms: W > 0, the t best by (W descending, component ascending), then in ascending component order
+    size_t n = 0;
+    for (size_t i = 0; i < touched.size(); ++i) {
+      const uint32_t c = touched[i];
+      seen[c] = 0;
+      if (W[c] > 0.0f) touched[n++] = c;   // (compacted in place: n <= i)
+      else W[c] = 0.0f;
+    }
+    const size_t keep = std::min<size_t>(t, n);
+    if (keep < n)
+      std::nth_element(touched.begin(), touched.begin() + (ptrdiff_t)keep, touched.begin() + (ptrdiff_t)n,
+                       [W](uint32_t a, uint32_t b) { return W[a] != W[b] ? W[a] > W[b] : a < b; });
+    std::sort(touched.begin(), touched.begin() + (ptrdiff_t)keep);
+    uint32_t* oc = out_comps + (size_t)q * t;
+    float* ov = out_vals + (size_t)q * t;
+    for (size_t i = 0; i < keep; ++i) {
+      oc[i] = touched[i];
+      ov[i] = W[touched[i]];
+    }
+    for (size_t i = keep; i < t; ++i) {
+      oc[i] = 0;
+      ov[i] = 0.0f;
+    }
+    out_n[q] = (uint32_t)keep;
+    for (size_t i = 0; i < n; ++i) W[touched[i]] = 0.0f;
   }
   return SGPU_OK;
 }

@@ -58,4 +58,30 @@ sgpu_status explain_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t bl
 sgpu_status explain_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t stream,
                                   const ExplainArgs& a);
 
+// ---- expand_queries.hip ----
+constexpr uint32_t kExpandBlock = 1024;   // threads of a workgroup (16 wavefronts: the kernel's wave totals are sized by it)
+struct ExpandArgs {
+  const uint8_t* fwd;         // the index, as ScoreArgs
+  const uint64_t* doc_ref;
+  const uint64_t* q_off;      // the call's staged queries and candidate offsets
+  const uint32_t* q_comp;
+  const float* q_val;
+  const uint64_t* cand_off;
+  const uint32_t* cand;       // the launch's candidate ids and weights: candidate i of the call at [i - cand_base]
+  const float* cand_w;
+  float* table;               // !DENSE: gridDim.x tables of dim + 1 floats (DENSE: the table is in LDS)
+  uint32_t* out_comps;        // the call's rows [nq x t] and counts
+  float* out_vals;
+  uint32_t* out_n;
+  uint64_t cand_base;
+  uint32_t q_first, q_last;   // the launch's queries [q_first, q_last)
+  uint32_t dim;
+  uint32_t t;
+  float alpha;
+  float val_scale;
+};
+// the expand kernel of (component width, value type, table form): as the explain kernel's pair above
+sgpu_status expand_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t lds, int* per_cu);
+sgpu_status expand_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t lds, hipStream_t stream, const ExpandArgs& a);
+
 }  // namespace sgpu

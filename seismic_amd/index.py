@@ -319,7 +319,8 @@ class _ScoreMixin:
     QueryEvaluator::compute_distance at src/posting_list.rs:210-211). A score is what search returns for the document,
     bit for bit. The classes supply _score_queries (queries -> CSR, unknown tokens dropped as in search),
     _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id);
-    explain / batch_explain (sgpu_explain_documents: the terms behind a score) also _score_token (component -> token)."""
+    explain / batch_explain (sgpu_explain_documents: the terms behind a score) and expand / batch_expand
+    (sgpu_expand_queries: Rocchio feedback queries) also _score_token (component -> token)."""
 
     def _score_csr(self, query_components, query_values, doc_ids_per_query):
         off, comps, vals = self._score_queries(query_components, query_values)
@@ -402,6 +403,36 @@ class _ScoreMixin:
     def explain(self, query_components, query_values, doc_ids, m=10, device=None):
         """(score, n_terms, [(token, query weight, document weight, product)]) of each of `doc_ids` for one query."""
         return self.batch_explain([query_components], [query_values], [doc_ids], m, device)[0]
+
+    def batch_expand(self, query_components, query_values, doc_ids_per_query, doc_weights_per_query=None, alpha=1.0,
+                     beta=0.75, terms=64, device=None):
+        """Rocchio feedback queries -> one (tokens, values) pair per query: alpha * query + sum over the feedback documents
+        doc_ids_per_query[q] of weight * document, the `terms` (1 .. 1024) heaviest positive components of it, in
+        ascending component order (values: float32 array). doc_weights_per_query[q][i] is the weight of document i of
+        query q; None: beta / len(doc_ids_per_query[q]) for each. Documents are added in the order given (f32 sums
+        depend on it), one listed twice is added twice. Tokens are mapped back through _score_token (the raw classes:
+        the integer component), so a pair can go to search / batch_search as it is. sgpu_expand_queries on the GPU the
+        index is on (device None) or its host twin (device False)."""
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        if doc_weights_per_query is None:
+            w = [np.full(len(r), np.float32(beta) / np.float32(len(r)), np.float32) if len(r) else np.zeros(0, np.float32)
+                 for r in rows]
+        else:
+            w = [np.asarray(x, np.float32).ravel() for x in doc_weights_per_query]
+            if [len(x) for x in w] != [len(r) for r in rows]:
+                raise ValueError("doc_weights_per_query does not match doc_ids_per_query")
+        cand_w = np.concatenate(w) if w else np.zeros(0, np.float32)
+        if self._score_on_device(device):
+            oc, ov, n = self._ix.expand_queries(off, comps, vals, cand_off, cand, cand_w, alpha, terms)
+        else:
+            oc, ov, n = self._ix.expand_queries_host(off, comps, vals, cand_off, cand, cand_w, alpha, terms)
+        token = self._score_token
+        return [([token(c) for c in oc[q, :m].tolist()], ov[q, :m].copy()) for q, m in enumerate(n.tolist())]
+
+    def expand(self, query_components, query_values, doc_ids, doc_weights=None, alpha=1.0, beta=0.75, terms=64, device=None):
+        """(tokens, values) of one query's feedback query (batch_expand)."""
+        return self.batch_expand([query_components], [query_values], [doc_ids], None if doc_weights is None else [doc_weights],
+                                 alpha, beta, terms, device)[0]
 
     def _batch_rerank_numpy(self, query_components, query_values, doc_ids_per_query, k, device):
         scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
@@ -672,6 +703,18 @@ class _IndexBase(_ScoreMixin):
         sc, ids, n = self._ix.batch_search(off, comps, vals, k, query_cut, heap_factor, first_sorted=bool(sorted),
                                            n_knn=n_knn, filter=f)
         return [self._remap(qids[i], sc[i], ids[i], n[i]) for i in range(len(qids))]
+
+    def batch_search_feedback(self, queries_ids, query_components, query_values, k, query_cut, heap_factor, fb_docs=10,
+                              fb_terms=64, alpha=1.0, beta=0.75, n_knn=0, sorted=True, filter=None):
+        """Pseudo-relevance feedback -> the rows of batch_search: search, batch_expand of every query with its first fb_docs
+        results as feedback documents (weight beta / their number), search again with the expanded queries. Composition
+        of the two calls, nothing else."""
+        first = self.batch_search(queries_ids, query_components, query_values, k, query_cut, heap_factor, n_knn=n_knn,
+                                  sorted=sorted, filter=filter)
+        docs = [[d for _, _, d in row[:int(fb_docs)]] for row in first]
+        expanded = self.batch_expand(query_components, query_values, docs, None, alpha, beta, fb_terms)
+        return self.batch_search(queries_ids, [np.asarray(t, dtype=str) for t, _ in expanded], [v for _, v in expanded], k,
+                                 query_cut, heap_factor, n_knn=n_knn, sorted=sorted, filter=filter)
 
     def batch_exact_search(self, queries_ids, query_components, query_values, k, device=None, filter=None):
         """Exact top-k over the index's own documents -> [[(query_id, score, doc_id)]] in input order, the rows of

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Register / spill / scratch figures of every search kernel variant (code object notes).
 # Usage: tools/kernel_resources.sh > profiles/<round>_kernel_resources.txt
+#        tools/kernel_resources.sh expand_queries.hip ...   (other translation units of seismic_amd/csrc, by name)
 cd "$(dirname "$0")/../seismic_amd/csrc" || exit 1
 TMP=$(mktemp -d)
-for f in sk_*.hip; do
+for f in ${@:-sk_*.hip}; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --offload-device-only --no-gpu-bundle-output -c "$f" -o "$TMP/${f%.hip}.co" -Wno-unknown-pragmas -Wno-unused-parameter &
 done
 wait
