@@ -533,6 +533,55 @@ sgpu_status sgpu_expand_queries_host(const sgpu_index* idx,
     float alpha, uint32_t t, uint32_t num_threads,
     uint32_t* out_comps, float* out_vals, uint32_t* out_n);
 
+/* ---- diversify: MMR selection of candidates -----------------------------------
+ * A result list that does not repeat itself: Maximal Marginal Relevance over each query's candidates, greedy, round by
+ * round, with document-against-document similarities computed on the device. The reference has no counterpart. Queries
+ * and candidates are given exactly as for sgpu_score_documents (any order, repeats allowed, possibly none).
+ * Relevance and similarity. rel(d) is the bits sgpu_score_documents returns for (query q, document d). sim(d, s), for a
+ * candidate d and an already selected document s, is the bits sgpu_score_documents returns for document d and the QUERY
+ * made of s's stored elements: one (component, weight) per stored element e < len(s), padding excluded, the weight the
+ * stored value as an f32 (binary16 widened, or code * val_scale; both exact); a stored value of +-0 contributes nothing,
+ * as a query weight of +-0 does. The streamed document is always the candidate d and the table always the selected s:
+ * sim(d, s) and sim(s, d) may differ in their last bits, and only the first is used. For FIXEDU8 / DOTVBYTE the product
+ * of an element is fl(fl((code_s * val_scale) * val_scale) * (float)code_d) (a val_scale^2 that underflows is outside
+ * this contract, as in explain and expand).
+ * Greedy selection, per query. Every candidate ENTRY (a place in the list) starts with pen = +0.0 and untaken. Round
+ * r = 0, 1, ...: among the untaken entries the one with the largest key (ordered(mmr bits) descending, document id
+ * ascending) is chosen, mmr = fl(fl(lambda * rel) - fl(mu * pen)): multiply, multiply, subtract, each rounded once,
+ * never contracted; ordered() is the monotone integer image of f32 bits of sgpu_explain_documents (-0.0 below +0.0).
+ * out_doc_ids[q, r] = its id, out_scores[q, r] = its rel, out_penalties[q, r] = its pen at the moment of selection (+0.0
+ * in round 0). Every entry with that id is marked taken: a document listed twice is selected once, and both its entries
+ * carry equal rel and pen throughout. Then, for every untaken entry d, pen(d) = max(pen(d), sim(d, selected)): pen is
+ * max(0, largest similarity to anything selected) - a negative similarity (signed stored values exist) never lowers the
+ * penalty below +0.0. The selection stops after k rounds or when no entry is untaken: out_n[q] = min(k, distinct
+ * candidates of q). Slots past out_n[q] are zero in all three nq x k row-major arrays; a query without candidates gets
+ * out_n = 0 and zeroed rows. Pairs whose rel, sim or mmr is not finite need not match the host twin.
+ * Consequences. With lambda = 1 and mu = 0, ids, scores and out_n are exactly those of sgpu_rerank_documents. The rows
+ * do not depend on the order in which the candidates are listed, nor on how the call is cut into launches.
+ * Checks, in this order: null arguments (SGPU_EINVAL; cand_ids and the four outputs too, also when there is nothing to
+ * do), everything sgpu_score_documents checks in its order, a lambda or mu that is not finite (SGPU_EINVAL), a query with
+ * more than 2048 listed candidates (SGPU_ELIMIT; the message names the query), a candidate document of more than 8192
+ * stored components (SGPU_ELIMIT: the most a half-full hash table in LDS holds, the bound the score call puts on a query;
+ * the message names the first such document and its query), k == 0 (SGPU_EINVAL), k > 256 (SGPU_ELIMIT), index not
+ * uploaded or replica out of range (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays usable). nq == 0 is
+ * SGPU_OK.
+ * The call shares the score calls' per-replica stream, mutex and recycled scratch and takes turns with them; it is safe
+ * beside searches, filtered and exact calls. It adds no index array; its scratch is freed by sgpu_index_destroy or a new
+ * upload. A launch takes whole queries only: SGPU_SCORE_CHUNK (candidates per launch, default 2^20) cuts between
+ * queries, a query of more candidates than that goes alone, and a run of queries without any candidate is no launch. */
+sgpu_status sgpu_diversify_documents(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids,
+    float lambda, float mu, uint32_t k,
+    float* out_scores, float* out_penalties, uint64_t* out_doc_ids, uint32_t* out_n);
+/* The same on the host cores (needs no upload): the arbiter of the contract above, the device call returns its bits;
+ * the same checks without the device ones. num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_diversify_documents_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids,
+    float lambda, float mu, uint32_t k, uint32_t num_threads,
+    float* out_scores, float* out_penalties, uint64_t* out_doc_ids, uint32_t* out_n);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

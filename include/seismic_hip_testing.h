@@ -61,6 +61,11 @@ sgpu_status sgpu_debug_score_stats(sgpu_index* idx, uint32_t replica, double* ou
  * 1 = the table in LDS / 0 = in global memory, grid of its last launch, workgroup size, LDS bytes, bytes of the global
  * tables (0 with the table in LDS), 0}; SGPU_EINVAL before the replica's first score or expand call */
 sgpu_status sgpu_debug_expand_stats(sgpu_index* idx, uint32_t replica, double* out8);
+/* what the last sgpu_diversify_documents call on `replica` measured: out8 = {device ms of its kernels (HIP events),
+ * launches, grid of its last launch, workgroup size, LDS bytes (table + entry state), 1 = dense table / 0 = hash, rounds of
+ * its longest query, 0}; SGPU_EINVAL before the replica's first score call. The environment name SGPU_DIVERSIFY_GRID, read
+ * per call and honoured under the same switch, lowers the grid (each workgroup then takes many queries in turn) */
+sgpu_status sgpu_debug_diversify_stats(sgpu_index* idx, uint32_t replica, double* out8);
 /* the accumulate launches of the last sgpu_exact_search_device[_filtered] call on `replica`: one per chunk of queries whose
  * candidates (n_ranges x k x 8 bytes per query) fit the candidate buffer of 256 MiB; the environment name
  * SGPU_EXACT_CAND_BYTES, read per call and honoured under the same switch, lowers that size. SGPU_EINVAL before the

@@ -95,6 +95,10 @@ def lib():
         L.sgpu_expand_queries.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32, vp, vp, vp]
         L.sgpu_expand_queries_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32, C.c_uint32, vp, vp,
                                                vp]
+        L.sgpu_diversify_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, C.c_float, C.c_float, C.c_uint32,
+                                               vp, vp, vp, vp]
+        L.sgpu_diversify_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_float, C.c_float, C.c_uint32,
+                                                    C.c_uint32, vp, vp, vp, vp]
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -547,6 +551,50 @@ class NativeIndex:
         check(fn(self.h, int(replica), _p(out)))
         return dict(kernel_ms=float(out[0]), launches=int(out[1]), dense=int(out[2]), grid=int(out[3]), block=int(out[4]),
                     lds=int(out[5]), table_bytes=int(out[6]))
+
+    # ---- MMR selection of candidates ----
+    @staticmethod
+    def _diversify_buffers(q_off, comps, vals, cand_off, cand_ids, k):
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        nq, k = len(q_off) - 1, int(k)
+        if not 0 <= k < 2 ** 32:
+            raise ValueError("k = %d" % k)
+        rows = (max(nq, 1), k if 1 <= k <= 256 else 1)   # (a k the library refuses: nothing is written)
+        sc, pen, ids = np.zeros(rows, np.float32), np.zeros(rows, np.float32), np.zeros(rows, np.uint64)
+        n = np.zeros(max(nq, 1), np.uint32)
+        cand = cand_ids if len(cand_ids) else np.zeros(1, np.uint64)
+        return q_off, comps, vals, cand_off, cand, nq, k, sc, pen, ids, n
+
+    def diversify_documents(self, q_off, comps, vals, cand_off, cand_ids, lam, mu, k, replica=0):
+        """sgpu_diversify_documents: per query the greedy MMR selection of at most k <= 256 DISTINCT documents among its
+        candidates (given as for score_documents, at most 2048 per query): round by round the candidate with the largest
+        lam * score - mu * (largest similarity to anything selected before, at least 0), ties by id ascending, scored and
+        selected on the device of `replica` (f32, see include/seismic_hip.h). Returns (scores f32 [nq, k], penalties f32
+        [nq, k], ids u64 [nq, k], n u32 [nq]); slots past n[q] are zero."""
+        q_off, comps, vals, cand_off, cand, nq, k, sc, pen, ids, n = self._diversify_buffers(q_off, comps, vals, cand_off,
+                                                                                             cand_ids, k)
+        check(lib().sgpu_diversify_documents(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand),
+                                             float(lam), float(mu), k, _p(sc), _p(pen), _p(ids), _p(n)))
+        return sc[:nq], pen[:nq], ids[:nq], n[:nq]
+
+    def diversify_documents_host(self, q_off, comps, vals, cand_off, cand_ids, lam, mu, k, num_threads=0):
+        """sgpu_diversify_documents_host: the same rows on the host cores (needs no upload), bit-identical."""
+        q_off, comps, vals, cand_off, cand, nq, k, sc, pen, ids, n = self._diversify_buffers(q_off, comps, vals, cand_off,
+                                                                                             cand_ids, k)
+        check(lib().sgpu_diversify_documents_host(self.h, _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand),
+                                                  float(lam), float(mu), k, int(num_threads), _p(sc), _p(pen), _p(ids), _p(n)))
+        return sc[:nq], pen[:nq], ids[:nq], n[:nq]
+
+    def debug_diversify_stats(self, replica=0):
+        """sgpu_debug_diversify_stats (test hook): what the last diversify_documents call on `replica` measured."""
+        out = np.zeros(8, np.float64)
+        fn = lib().sgpu_debug_diversify_stats
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        check(fn(self.h, int(replica), _p(out)))
+        return dict(kernel_ms=float(out[0]), launches=int(out[1]), grid=int(out[2]), block=int(out[3]), lds=int(out[4]),
+                    dense=int(out[5]), rounds=int(out[6]))
 
 
 def _filter_handle(f):

@@ -76,6 +76,10 @@ sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint6
                                   uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
                                   uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
 bool expand_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+sgpu_status diversify_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                       const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
+                                       float mu, uint32_t k, const DiversifyOut& out);
+bool diversify_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
 const sgpu_index* filter_index(const sgpu_filter* f);
@@ -915,6 +919,33 @@ sgpu_status sgpu_expand_queries_host(const sgpu_index* idx, const uint64_t* q_of
   if (!idx) return fail(SGPU_EINVAL, "null argument");
   return expand_queries_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha, t, num_threads, out_comps,
                              out_vals, out_n);
+}
+
+sgpu_status sgpu_diversify_documents(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                     const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
+                                     float mu, uint32_t k, float* out_scores, float* out_penalties, uint64_t* out_doc_ids,
+                                     uint32_t* out_n) {
+  const DiversifyOut out{out_scores, out_penalties, out_doc_ids, out_n};
+  return diversify_documents_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, lambda, mu, k, out);
+}
+
+sgpu_status sgpu_diversify_documents_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                          uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu,
+                                          uint32_t k, uint32_t num_threads, float* out_scores, float* out_penalties,
+                                          uint64_t* out_doc_ids, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  const DiversifyOut out{out_scores, out_penalties, out_doc_ids, out_n};
+  return diversify_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, lambda, mu, k, num_threads, out);
+}
+
+// (not part of the boundary: what the last sgpu_diversify_documents call on `replica` measured - out8 = {device ms of its
+// kernels, launches, grid of the last launch, workgroup size, LDS bytes, 1 = dense table / 0 = hash, rounds of its longest
+// query, 0}; SGPU_EINVAL before the replica's first score call. tools/diversify_probe.py)
+sgpu_status sgpu_debug_diversify_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");
+  if (!diversify_debug_stats(idx, replica, out8)) return fail(SGPU_EINVAL, "no diversify call has run on replica %u", replica);
+  return SGPU_OK;
 }
 
 // (not part of the boundary: what the last sgpu_expand_queries call on `replica` measured - out8 = {device ms of its kernels,

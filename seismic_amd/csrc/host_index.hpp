@@ -133,6 +133,22 @@ sgpu_status expand_check_args(const HostIndex& h, const uint64_t* q_off, const u
 sgpu_status expand_queries_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                 const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha, uint32_t t,
                                 uint32_t num_threads, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
+// MMR selection of candidates (sgpu_diversify_documents_host) and checks 1 - 7 both diversify calls run
+constexpr uint32_t kDiversifyMaxK = 256;
+constexpr uint64_t kDiversifyMaxCand = 2048;   // listed candidates of one query (the device keeps their state in LDS)
+struct DiversifyOut {   // the outputs of a diversify call: rows of k and a count per query
+  float* scores;
+  float* penalties;
+  uint64_t* doc_ids;
+  uint32_t* n;
+};
+// (*max_len = the stored components of the longest candidate document, *max_cand = the candidates of the longest list)
+sgpu_status diversify_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                 const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
+                                 const DiversifyOut& out, uint32_t* max_nnz, uint32_t* max_len, uint32_t* max_cand);
+sgpu_status diversify_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                     const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
+                                     uint32_t num_threads, const DiversifyOut& out);
 // score_documents.hip
 void score_state_free(ScoreState* s);
 

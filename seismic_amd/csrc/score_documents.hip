@@ -50,6 +50,10 @@
 // sgpu_expand_queries has a launcher of its own, expand_run, because its unit of work is a whole query and not a tile of
 // candidates: it cuts between queries only. It shares ScoreState with score_run - the stream, the mutex, the staged
 // queries and ids - and adds the buffers its rows and tables need; the kernel is expand_queries.hip's.
+//
+// sgpu_diversify_documents (MMR selection) has diversify_run, cut between queries as expand_run cuts: a workgroup of
+// diversify_documents.hip's kernel keeps a whole query's entries in LDS. Its rows lie in rerank's row buffers plus one
+// for the penalties.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -320,6 +324,7 @@ struct ScoreState {
   // expand: the call's candidate offsets and rows (components, values, counts), a launch's candidate weights and, where
   // the table does not fit LDS, one table per workgroup
   DeviceBuffer x_cand_off, x_comps, x_vals, x_n, x_w, x_table;
+  DeviceBuffer d_pen;           // diversify: the call's penalty rows (scores, ids and counts: rerank's row buffers)
   std::vector<uint4> h_tiles;   // host staging of a launch
   std::vector<uint32_t> h_ids;
   std::vector<std::vector<SelTask>> sel_rounds;   // [round * tiers + tier]
@@ -331,6 +336,8 @@ struct ScoreState {
   double x_kernel_ms = 0;       // the same of the last expand call (sgpu_debug_expand_stats)
   uint32_t x_launches = 0, x_dense = 0, x_grid = 0, x_lds = 0;
   uint64_t x_table_bytes = 0;
+  double d_kernel_ms = 0;       // the same of the last diversify call (sgpu_debug_diversify_stats)
+  uint32_t d_launches = 0, d_dense = 0, d_grid = 0, d_lds = 0, d_rounds = 0;
 };
 
 void score_state_free(ScoreState* s) {
@@ -339,7 +346,7 @@ void score_state_free(ScoreState* s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (DeviceBuffer* b : {&s->q_off, &s->q_comp, &s->q_val, &s->tiles, &s->cand, &s->scores, &s->sel_tasks, &s->slots, &s->carry,
                           &s->row_scores, &s->row_ids, &s->row_n, &s->terms, &s->x_cand_off, &s->x_comps, &s->x_vals, &s->x_n,
-                          &s->x_w, &s->x_table})
+                          &s->x_w, &s->x_table, &s->d_pen})
     b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -878,6 +885,152 @@ sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint6
   } catch (const std::bad_alloc&) {
     return fail(SGPU_ENOMEM, "out of host memory");
   }
+}
+
+// ---- sgpu_diversify_documents ----
+// A diversify call: diversify_documents.hip's kernel over the call's queries, staged and cut as expand_run stages and
+// cuts them - a launch takes whole queries, consecutive ones while their candidates fit the budget (SGPU_SCORE_CHUNK), a
+// larger query alone -; the call's rows stay on the device until its end, zeroed before the first launch.
+static sgpu_status diversify_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
+                                 const float* vals, uint32_t nq, uint32_t max_nnz, uint32_t max_len, uint32_t max_cand,
+                                 const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
+                                 const DiversifyOut& out) {
+  HIP_TRY(hipSetDevice(s->device));
+  s->d_kernel_ms = 0;
+  s->d_launches = 0;
+  s->d_rounds = 0;
+  // the table: the score kernel's rule and its test hook; the hash table holds the longest query or candidate document
+  const uint64_t dense_bytes = ((h.dim + 1) * 4 + 15) & ~15ull;
+  bool dense = dense_bytes <= kScoreDenseLds;
+  if (test_hooks_on()) {
+    const char* v = std::getenv("SGPU_SCORE_LOOKUP");
+    if (v && *v == '2') dense = false;
+  }
+  uint32_t slot_bits = 6;
+  while ((1u << slot_bits) < 2u * std::max(max_nnz, max_len)) ++slot_bits;   // (both <= 8192: at most 2^14 slots, 128 KiB)
+  const uint32_t table_bytes = dense ? (uint32_t)dense_bytes : (8u << slot_bits);
+  const uint32_t cap = std::max(64u, (max_cand + 63u) & ~63u);   // (<= 2048: 24 KiB of entry state)
+  const uint32_t lds = table_bytes + cap * 12u;
+  int per_cu = 0;
+  sgpu_status st;
+  if ((st = diversify_kernel_fit(h.comp_width, h.value_type, dense, lds, &per_cu)) != SGPU_OK) return st;
+  if (per_cu < 1) return fail(SGPU_ELIMIT, "the diversify kernel does not fit on a CU (%u bytes of LDS)", lds);
+  per_cu = std::min(per_cu, (int)(2048u / kDiversifyBlock));
+  uint64_t max_grid = (uint64_t)s->n_cu * (uint32_t)per_cu;
+  if (test_hooks_on())   // (test hook SGPU_DIVERSIFY_GRID: fewer workgroups, so that each takes many queries in turn)
+    if (const char* v = std::getenv("SGPU_DIVERSIFY_GRID"))
+      if (*v) max_grid = std::max<uint64_t>(1, std::min<uint64_t>(max_grid, std::strtoull(v, nullptr, 10)));
+
+  uint64_t budget = kScoreChunk;
+  if (const char* v = std::getenv("SGPU_SCORE_CHUNK"))
+    if (*v) budget = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  budget = std::min<uint64_t>(budget, 1ull << 28);
+
+  const uint64_t qnnz = q_off[nq], cells = (uint64_t)nq * k;
+  if ((st = score_reserve(s, s->q_off, (uint64_t)(nq + 1) * 8)) != SGPU_OK || (st = score_reserve(s, s->q_comp, qnnz * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->q_val, qnnz * 4)) != SGPU_OK || (st = score_reserve(s, s->x_cand_off, (uint64_t)(nq + 1) * 8)) != SGPU_OK ||
+      (st = score_reserve(s, s->row_scores, cells * 4)) != SGPU_OK || (st = score_reserve(s, s->d_pen, cells * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->row_ids, cells * 8)) != SGPU_OK || (st = score_reserve(s, s->row_n, (uint64_t)nq * 4)) != SGPU_OK)
+    return st;
+  HIP_TRY(hipMemcpyAsync(s->q_off.p, q_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->x_cand_off.p, cand_off, (uint64_t)(nq + 1) * 8, hipMemcpyHostToDevice, s->stream));
+  if (qnnz) {
+    HIP_TRY(hipMemcpyAsync(s->q_comp.p, comps, qnnz * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->q_val.p, vals, qnnz * 4, hipMemcpyHostToDevice, s->stream));
+  }
+  HIP_TRY(hipMemsetAsync(s->row_scores.p, 0, cells * 4, s->stream));
+  HIP_TRY(hipMemsetAsync(s->d_pen.p, 0, cells * 4, s->stream));
+  HIP_TRY(hipMemsetAsync(s->row_ids.p, 0, cells * 8, s->stream));
+  HIP_TRY(hipMemsetAsync(s->row_n.p, 0, (uint64_t)nq * 4, s->stream));
+  DiversifyArgs a{};
+  a.fwd = view.fwd;
+  a.doc_ref = view.doc_ref;
+  a.q_off = s->q_off.as<const uint64_t>();
+  a.q_comp = s->q_comp.as<const uint32_t>();
+  a.q_val = s->q_val.as<const float>();
+  a.cand_off = s->x_cand_off.as<const uint64_t>();
+  a.row_scores = s->row_scores.as<float>();
+  a.row_pen = s->d_pen.as<float>();
+  a.row_ids = s->row_ids.as<uint64_t>();
+  a.row_n = s->row_n.as<uint32_t>();
+  a.dim = (uint32_t)h.dim;
+  a.slot_bits = slot_bits;
+  a.table_bytes = table_bytes;
+  a.cap = cap;
+  a.k = k;
+  a.lambda = lambda;
+  a.mu = mu;
+  a.val_scale = h.val_scale;
+  s->d_dense = dense;
+  s->d_lds = lds;
+
+  for (uint32_t q = 0; q < nq;) {
+    const uint32_t qa = q;
+    const uint64_t first = cand_off[qa];
+    ++q;   // (a query of more candidates than the budget goes alone)
+    while (q < nq && cand_off[q + 1] - first <= budget) ++q;
+    const uint64_t n_cand = cand_off[q] - first;   // (<= max(budget, kDiversifyMaxCand) < 2^32)
+    if (n_cand == 0) continue;   // (queries without candidates: their rows are zero already)
+    s->h_ids.resize(n_cand);
+    for (uint64_t i = 0; i < n_cand; ++i) s->h_ids[i] = (uint32_t)cand_ids[first + i];
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(q - qa, max_grid);
+    if ((st = score_reserve(s, s->cand, n_cand * 4)) != SGPU_OK) return st;
+    HIP_TRY(hipMemcpyAsync(s->cand.p, s->h_ids.data(), n_cand * 4, hipMemcpyHostToDevice, s->stream));
+    a.cand = s->cand.as<const uint32_t>();
+    a.cand_base = first;
+    a.q_first = qa;
+    a.q_last = q;
+    s->d_grid = grid;
+    HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    if ((st = diversify_kernel_launch(h.comp_width, h.value_type, dense, grid, lds, s->stream, a)) != SGPU_OK) return st;
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (the staged ids are the next launch's)
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->d_kernel_ms += ms;
+    s->d_launches += 1;
+  }
+  HIP_TRY(hipMemcpyAsync(out.scores, s->row_scores.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out.penalties, s->d_pen.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out.doc_ids, s->row_ids.p, cells * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out.n, s->row_n.p, (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (uint32_t i = 0; i < nq; ++i) s->d_rounds = std::max(s->d_rounds, out.n[i]);
+  return SGPU_OK;
+}
+
+sgpu_status diversify_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                       const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
+                                       float mu, uint32_t k, const DiversifyOut& out) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  uint32_t max_nnz = 0, max_len = 0, max_cand = 0;
+  const sgpu_status vst =
+      diversify_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, lambda, mu, k, out, &max_nnz, &max_len, &max_cand);
+  if (vst != SGPU_OK) return vst;
+  ScoreState* s = nullptr;
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
+  if (nq == 0) return SGPU_OK;
+  std::lock_guard<std::mutex> lk(s->mu);
+  try {
+    return diversify_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, max_nnz, max_len, max_cand,
+                         cand_off, cand_ids, lambda, mu, k, out);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+// (test hook: what the last diversify call on `replica` measured - out8 = {device ms of its kernels, launches, grid of the last
+// launch, workgroup size, LDS bytes, 1 = dense table / 0 = hash, rounds of its longest query, 0}. tools/diversify_probe.py)
+bool diversify_debug_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  std::lock_guard<std::mutex> lk(idx->score_mu);
+  if (replica >= idx->score.size() || !idx->score[replica]) return false;
+  ScoreState* s = idx->score[replica];
+  std::lock_guard<std::mutex> lk2(s->mu);
+  const double v[8] = {s->d_kernel_ms, (double)s->d_launches, (double)s->d_grid, (double)kDiversifyBlock,
+                       (double)s->d_lds,  (double)s->d_dense,    (double)s->d_rounds, 0.0};
+  for (int i = 0; i < 8; ++i) out8[i] = v[i];
+  return true;
 }
 
 // (test hook: what the last expand call on `replica` measured - out8 = {device ms of its kernels, launches, 1 = table in LDS /

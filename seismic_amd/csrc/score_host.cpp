@@ -1,5 +1,5 @@
-// score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host, sgpu_explain_documents_host and
-// sgpu_expand_queries_host, and the argument checks they share with the device calls.
+// score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host, sgpu_explain_documents_host,
+// sgpu_expand_queries_host and sgpu_diversify_documents_host, and the argument checks they share with the device calls.
 //
 // The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
@@ -393,6 +393,116 @@ sgpu_status expand_queries_host(const HostIndex& h, const uint64_t* q_off, const
     }
     out_n[q] = (uint32_t)keep;
     for (size_t i = 0; i < n; ++i) W[touched[i]] = 0.0f;
+  }
+  return SGPU_OK;
+}
+
+// Checks 1 - 7 of sgpu_diversify_documents, in the header's order.
+sgpu_status diversify_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                 const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
+                                 const DiversifyOut& out, uint32_t* max_nnz, uint32_t* max_len, uint32_t* max_cand) {
+  if (!out.penalties || !out.doc_ids || !out.n) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out.scores, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  if (!std::isfinite(lambda)) return fail(SGPU_EINVAL, "lambda is not finite");
+  if (!std::isfinite(mu)) return fail(SGPU_EINVAL, "mu is not finite");
+  *max_len = 0;
+  *max_cand = 0;
+  for (uint32_t q = 0; q < nq; ++q) {
+    if (cand_off[q + 1] - cand_off[q] > kDiversifyMaxCand)
+      return fail(SGPU_ELIMIT, "query %u has %llu candidates (diversifying documents: limit %llu)", q,
+                  (unsigned long long)(cand_off[q + 1] - cand_off[q]), (unsigned long long)kDiversifyMaxCand);
+    *max_cand = std::max(*max_cand, (uint32_t)(cand_off[q + 1] - cand_off[q]));
+  }
+  for (uint32_t q = 0; q < nq; ++q)
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
+      const uint64_t len = h.fwd_offsets[cand_ids[i] + 1] - h.fwd_offsets[cand_ids[i]];
+      if (len > kScoreMaxQueryNnz)
+        return fail(SGPU_ELIMIT, "query %u: document id %llu has %llu components (diversifying documents: limit %u)", q,
+                    (unsigned long long)cand_ids[i], (unsigned long long)len, kScoreMaxQueryNnz);
+      *max_len = std::max(*max_len, (uint32_t)len);
+    }
+  if (k == 0) return fail(SGPU_EINVAL, "k must be at least 1");
+  if (k > kDiversifyMaxK) return fail(SGPU_ELIMIT, "k = %u (diversifying documents: limit %u)", k, kDiversifyMaxK);
+  return SGPU_OK;
+}
+
+// The host twin of diversify_documents.hip, the arbiter of its rows: the greedy selection of the header, entry by entry.
+// rel and sim both come from score_one - sim with the selected document's stored vector scattered into the thread's
+// table in the query's place (fixed-u8: its value code * val_scale, then the fold of val_scale score_documents_host
+// applies to every query weight) -, so a row is made of the bits sgpu_score_documents_host returns.
+sgpu_status diversify_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                     const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
+                                     uint32_t num_threads, const DiversifyOut& out) {
+  uint32_t max_nnz = 0, max_len = 0, max_cand = 0;
+  const sgpu_status vst =
+      diversify_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, lambda, mu, k, out, &max_nnz, &max_len, &max_cand);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0) return SGPU_OK;
+  std::memset(out.scores, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.penalties, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.doc_ids, 0, (size_t)nq * k * sizeof(uint64_t));
+  std::memset(out.n, 0, (size_t)nq * sizeof(uint32_t));
+  if (cand_off[nq] == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  struct Entry {
+    uint64_t id;
+    float rel, pen;
+    bool taken;
+  };
+  std::vector<std::vector<float>> tables;
+  std::vector<std::vector<Entry>> entries;
+  try {
+    tables.assign((size_t)team, std::vector<float>());
+    for (auto& t : tables) t.assign(h.dim, 0.0f);
+    entries.assign((size_t)team, std::vector<Entry>());
+    for (auto& v : entries) v.reserve(max_cand);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+    if (cand_off[q + 1] == cand_off[q]) continue;
+#ifdef _OPENMP
+    const size_t me = (size_t)omp_get_thread_num();
+#else
+    const size_t me = 0;
+#endif
+    float* dense = tables[me].data();
+    std::vector<Entry>& en = entries[me];   // (reserved for the longest list: nothing below allocates)
+    en.clear();
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) en.push_back(Entry{cand_ids[i], score_one(h, cand_ids[i], dense), 0.0f, false});
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+    size_t left = en.size();
+    uint32_t r = 0;
+    while (r < k && left) {
+      uint64_t best = 0;
+      const Entry* pick = nullptr;
+      for (const Entry& e : en) {
+        if (e.taken) continue;
+        const float a = lambda * e.rel, b = mu * e.pen;
+        const float mmr = a - b;
+        const uint64_t key = ((uint64_t)ordered_bits(mmr) << 32) | (uint64_t)(~(uint32_t)e.id);
+        if (!pick || key > best) best = key, pick = &e;
+      }
+      const uint64_t sel = pick->id;
+      out.doc_ids[(size_t)q * k + r] = sel;
+      out.scores[(size_t)q * k + r] = pick->rel;
+      out.penalties[(size_t)q * k + r] = pick->pen;
+      ++r;
+      for (Entry& e : en)
+        if (!e.taken && e.id == sel) e.taken = true, --left;
+      if (r == k || !left) break;
+      const uint64_t s0 = h.fwd_offsets[sel], s1 = h.fwd_offsets[sel + 1];
+      for (uint64_t x = s0; x < s1; ++x) dense[h.comp(x)] = f16 ? f16_to_f32(h.fwd_vals[x]) : h.val(x) * h.val_scale;
+      for (Entry& e : en)
+        if (!e.taken) e.pen = std::fmax(e.pen, score_one(h, e.id, dense));
+      for (uint64_t x = s0; x < s1; ++x) dense[h.comp(x)] = 0.0f;
+    }
+    out.n[q] = r;
   }
   return SGPU_OK;
 }

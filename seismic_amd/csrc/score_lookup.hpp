@@ -84,4 +84,33 @@ struct ExpandArgs {
 sgpu_status expand_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t lds, int* per_cu);
 sgpu_status expand_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t lds, hipStream_t stream, const ExpandArgs& a);
 
+// ---- diversify_documents.hip ----
+constexpr uint32_t kDiversifyBlock = 1024;   // threads of a workgroup (16 wavefronts: the kernel's wave maxima are sized by it)
+struct DiversifyArgs {
+  const uint8_t* fwd;         // the index, as ScoreArgs
+  const uint64_t* doc_ref;
+  const uint64_t* q_off;      // the call's staged queries and candidate offsets
+  const uint32_t* q_comp;
+  const float* q_val;
+  const uint64_t* cand_off;
+  const uint32_t* cand;       // the launch's candidate ids: candidate i of the call at [i - cand_base]
+  float* row_scores;          // the call's rows [nq x k] (zeroed before the first launch) and counts
+  float* row_pen;
+  uint64_t* row_ids;
+  uint32_t* row_n;
+  uint64_t cand_base;
+  uint32_t q_first, q_last;   // the launch's queries [q_first, q_last)
+  uint32_t dim;
+  uint32_t slot_bits;         // hash table: log2 of its slots (sized for the longest query AND the longest candidate document)
+  uint32_t table_bytes;       // LDS: the table, then the entry state - ids, rels, pens of `cap` entries each
+  uint32_t cap;               // >= the candidates of every query of the call
+  uint32_t k;
+  float lambda, mu;
+  float val_scale;
+};
+// the diversify kernel of (component width, value type, table form): as the explain kernel's pair above
+sgpu_status diversify_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t lds, int* per_cu);
+sgpu_status diversify_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t lds, hipStream_t stream,
+                                    const DiversifyArgs& a);
+
 }  // namespace sgpu

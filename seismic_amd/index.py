@@ -320,7 +320,8 @@ class _ScoreMixin:
     bit for bit. The classes supply _score_queries (queries -> CSR, unknown tokens dropped as in search),
     _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id);
     explain / batch_explain (sgpu_explain_documents: the terms behind a score) and expand / batch_expand
-    (sgpu_expand_queries: Rocchio feedback queries) also _score_token (component -> token)."""
+    (sgpu_expand_queries: Rocchio feedback queries) also _score_token (component -> token); diversify / batch_diversify
+    (sgpu_diversify_documents: MMR selection) need what rerank needs."""
 
     def _score_csr(self, query_components, query_values, doc_ids_per_query):
         off, comps, vals = self._score_queries(query_components, query_values)
@@ -434,7 +435,26 @@ class _ScoreMixin:
         return self.batch_expand([query_components], [query_values], [doc_ids], None if doc_weights is None else [doc_weights],
                                  alpha, beta, terms, device)[0]
 
-    def _batch_rerank_numpy(self, query_components, query_values, doc_ids_per_query, k, device):
+    def batch_diversify(self, query_components, query_values, doc_ids_per_query, k, lam=0.5, mu=0.5, device=None):
+        """Maximal Marginal Relevance over each query's candidates -> [[(score, penalty, doc_id)]] in selection order: round
+        by round the candidate with the largest lam * score - mu * penalty, where penalty is its largest similarity (dot
+        product of the stored vectors) to anything selected before, at least 0; ties by native document id ascending, a
+        candidate given more than once counted once. k: 1 .. 256; at most 2048 candidates per query. lam = 1, mu = 0 is
+        batch_rerank. sgpu_diversify_documents on the GPU the index is on (device None) or its host twin (device False)."""
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        if self._score_on_device(device):
+            sc, pen, ids, n = self._ix.diversify_documents(off, comps, vals, cand_off, cand, lam, mu, k)
+        else:
+            sc, pen, ids, n = self._ix.diversify_documents_host(off, comps, vals, cand_off, cand, lam, mu, k)
+        sc, pen, ids = sc.tolist(), pen.tolist(), ids.tolist()
+        name = self._score_name
+        return [[(s, p, name(d)) for s, p, d in zip(sc[q][:m], pen[q][:m], ids[q][:m])] for q, m in enumerate(n.tolist())]
+
+    def diversify(self, query_components, query_values, doc_ids, k, lam=0.5, mu=0.5, device=None):
+        """The MMR selection among the documents `doc_ids` for one query -> [(score, penalty, doc_id)] (batch_diversify)."""
+        return self.batch_diversify([query_components], [query_values], [doc_ids], k, lam, mu, device)[0]
+
+    def _batch_rerank_numpy(self,query_components, query_values, doc_ids_per_query, k, device):
         scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
         out = []
         for sc, r in zip(scores, rows):
