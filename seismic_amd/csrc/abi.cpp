@@ -72,10 +72,12 @@ sgpu_status explain_documents_device(sgpu_index* idx, uint32_t replica, const ui
                                      const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
                                      const ExplainOut& out);
 bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+// expand_queries.hip
 sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
                                   uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
                                   uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
 bool expand_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+// diversify_documents.hip
 sgpu_status diversify_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                        const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
                                        float mu, uint32_t k, const DiversifyOut& out);

@@ -1,5 +1,5 @@
-// device_prims.hpp — the small device functions the kernels beside the search kernels share (exact_device.hip,
-// score_documents.hip, filter.hip, build_summaries.hip, build_assign.hip): one definition each. The binary16 conversion
+// device_prims.hpp — the small device functions the kernels beside the search kernels share (exact_device.hip, the
+// candidate calls' units through score_lookup.hpp, filter.hip, build_summaries.hip, build_assign.hip): one definition each. The binary16 conversion
 // is record.hpp's half_bits_to_float.
 #pragma once
 #include "record.hpp"
@@ -21,6 +21,34 @@ SGPU_DEV uint32_t wave_incl_scan(uint32_t v) {
   for (uint32_t o = 1; o < 64; o <<= 1) {
     const uint32_t t = __shfl_up(v, o, 64);
     if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// Reductions over a 16-lane group (xor shuffles, strides 8, 4, 2, 1: every lane ends with the result), for the kernels in
+// which a group owns a document. The f32 sum is the canonical one of a score: t[j] += t[j ^ s], each step rounded once.
+SGPU_DEV float group16_sum(float v) {
+  v = __fadd_rn(v, __shfl_xor(v, 8, 16));
+  v = __fadd_rn(v, __shfl_xor(v, 4, 16));
+  v = __fadd_rn(v, __shfl_xor(v, 2, 16));
+  v = __fadd_rn(v, __shfl_xor(v, 1, 16));
+  return v;
+}
+SGPU_DEV uint32_t group16_sum(uint32_t v) {
+#pragma unroll
+  for (int s = 8; s >= 1; s >>= 1) v += __shfl_xor(v, s, 16);
+  return v;
+}
+SGPU_DEV uint32_t group16_or(uint32_t v) {
+#pragma unroll
+  for (int s = 8; s >= 1; s >>= 1) v |= __shfl_xor(v, s, 16);
+  return v;
+}
+SGPU_DEV uint64_t group16_max(uint64_t v) {
+#pragma unroll
+  for (int s = 8; s >= 1; s >>= 1) {
+    const uint64_t o = __shfl_xor(v, s, 16);
+    v = o > v ? o : v;
   }
   return v;
 }

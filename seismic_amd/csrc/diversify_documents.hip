@@ -12,15 +12,13 @@
 //   table   has one occupant at a time: the query (phase 0) or the document selected last (rounds). Before the next
 //           occupant moves in the table is emptied of the previous one - dense: sparsely, by walking the occupant's
 //           components again; hash: wholesale. A document moves in decoded once by the workgroup, its passes of 128
-//           elements over the 16-lane groups (record.hpp, as expand_queries.hip walks a document), the weight of
+//           elements over the 16-lane groups (workgroup_walk_doc, as expand_queries.hip walks a document), the weight of
 //           element e the f32 its stored bits stand for (fixed-u8: fl(fl(code * val_scale) * val_scale), the query
 //           weight code * val_scale with the score kernel's fold of val_scale on top); elements e >= len (slice padding)
 //           are MASKED, since a padding element repeats a component whose real element another lane holds. A
-//           document's components are distinct: dense stores do not collide, the hash arm inserts with the score
-//           kernel's CAS loop.
-//   stream  both phases score entries against the table exactly as score_documents_kernel does: a 16-lane group per
-//           entry, kDivDocs entries per group in flight, load_pass / slice_components / raw_pass_components /
-//           place_values / weight_of, accumulator order and shuffle reduction unchanged. Phase 0 writes rel; a round
+//           document's components are distinct: dense stores do not collide, the hash arm inserts with table_put.
+//   stream  both phases score entries against the table with score_lookup.hpp's group_score, the score kernel's own
+//           loop: a 16-lane group per entry, kDivDocs entries per group in flight. Phase 0 writes rel; a round
 //           raises pen with fmaxf (pen starts at +0.0, so a negative similarity never lowers it) and skips the taken.
 //   argmax  every thread forms the keys of its entries (at most two), a wave reduction by shuffles, the 16 wave maxima
 //           through LDS. The entries that carry the selected id are marked taken (pen = kTaken, the bits of no pen: a
@@ -36,11 +34,36 @@
 
 #include <type_traits>
 
-#include "score_lookup.hpp"
+#include "score_state.hpp"
 
 namespace sgpu {
 
 namespace {
+
+constexpr uint32_t kDiversifyBlock = 1024;   // threads of a workgroup (16 wavefronts: the kernel's wave maxima are sized by it)
+
+struct DiversifyArgs {
+  const uint8_t* fwd;         // DevView::fwd and doc_ref
+  const uint64_t* doc_ref;
+  const uint64_t* q_off;      // the call's staged queries and candidate offsets
+  const uint32_t* q_comp;
+  const float* q_val;
+  const uint64_t* cand_off;
+  const uint32_t* cand;       // the launch's candidate ids: candidate i of the call at [i - cand_base]
+  float* row_scores;          // the call's rows [nq x k] (zeroed before the first launch) and counts
+  float* row_pen;
+  uint64_t* row_ids;
+  uint32_t* row_n;
+  uint64_t cand_base;
+  uint32_t q_first, q_last;   // the launch's queries [q_first, q_last)
+  uint32_t dim;
+  uint32_t slot_bits;         // hash table: log2 of its slots (sized for the longest query AND the longest candidate document)
+  uint32_t table_bytes;       // LDS: the table, then the entry state - ids, rels, pens of `cap` entries each
+  uint32_t cap;               // >= the candidates of every query of the call
+  uint32_t k;
+  float lambda, mu;
+  float val_scale;
+};
 
 constexpr uint32_t kDivWaves = kDiversifyBlock / 64u;
 constexpr uint32_t kDivGroups = kDiversifyBlock / 16u;
@@ -54,107 +77,30 @@ struct DivState {   // the entries of the workgroup's query, in LDS behind the t
   uint32_t* pen;    // f32 bits, or kTaken
 };
 
-// The document `ref` into the table (FILL) or out of a dense table again (!FILL), by the whole workgroup.
-template <typename CT, int VT, bool DENSE, bool FILL>
-__device__ __forceinline__ void table_walk_doc(const DiversifyArgs& a, uint8_t* smem, uint64_t ref) {
-  const uint32_t tid = threadIdx.x, g = tid >> 4, l = tid & 15u;
-  const uint32_t len = (uint32_t)ref & LenMask<VT>::v;
-  const bool raw = Vt<VT>::sliced && ((uint32_t)ref & kRawBit) != 0u;
-  const uint8_t* rec = a.fwd + (size_t)(ref >> 16) * 16u;
-  const uint32_t slots = 1u << a.slot_bits;
-  for (uint32_t p0 = g * 128u; p0 < len; p0 += kDivGroups * 128u) {
-    const uint32_t e0 = p0 + l * 8u;
-    if (e0 >= len) continue;
-    DocChunk<CT, VT> d;
-    load_pass<CT, VT>(d, rec, len, raw, e0);
-    uint32_t c[8];
-    if (Vt<VT>::sliced && raw) {
-      raw_pass_components<CT, VT>(d, c);
-    } else {
-      slice_components<CT, VT>(d, c);
-    }
-    place_values<CT, VT>(d, raw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (e0 + (uint32_t)i < len) {   // (padding elements are no part of the document)
-        if (!FILL) {
-          ((float*)smem)[c[i]] = 0.0f;
-          continue;
-        }
-        const float v = slice_value<VT>(d.v, i);
-        const float w = Vt<VT>::half ? v : __fmul_rn(__fmul_rn(v, a.val_scale), a.val_scale);
-        if (DENSE) {
-          ((float*)smem)[c[i]] = w;
-        } else {
-          uint32_t* keys = (uint32_t*)smem;
-          float* wts = (float*)(smem + (size_t)slots * 4u);
-          uint32_t slot = (c[i] * 2654435761u) >> (32u - a.slot_bits);
-          while (atomicCAS(&keys[slot], kHashEmpty, c[i]) != kHashEmpty) slot = (slot + 1u) & (slots - 1u);
-          wts[slot] = w;
-        }
-      }
-  }
-}
-
 // Entries [0, n) that are not taken against the table, as score_documents_kernel scores a tile. REL: the result is the
 // entry's rel; else its pen is raised to it.
 template <typename CT, int VT, bool DENSE, bool REL>
-__device__ __forceinline__ void stream_entries(const DiversifyArgs& a, const uint8_t* smem, const DivState& st, uint32_t n) {
+__device__ __forceinline__ void stream_entries(const DiversifyArgs& a, const WeightTable& tab, const DivState& st, uint32_t n) {
   const uint32_t tid = threadIdx.x, g = tid >> 4, l = tid & 15u;
   for (uint32_t base = 0; base < n; base += kDivGroups * kDivDocs) {
-    uint32_t len[kDivDocs], idx[kDivDocs];
-    const uint8_t* rec[kDivDocs];
-    bool raw[kDivDocs], live[kDivDocs];
-    float acc[kDivDocs];
-    uint32_t max_len = 0;
+    uint32_t idx[kDivDocs];
+    bool live[kDivDocs];
+    DocRef<VT> doc[kDivDocs];
 #pragma unroll
     for (uint32_t u = 0; u < kDivDocs; ++u) {
       idx[u] = base + u * kDivGroups + g;
       live[u] = idx[u] < n && (REL || st.pen[idx[u]] != kTaken);
-      const uint64_t ref = live[u] ? a.doc_ref[st.id[idx[u]]] : 0ull;
-      len[u] = (uint32_t)ref & LenMask<VT>::v;
-      raw[u] = Vt<VT>::sliced && ((uint32_t)ref & kRawBit) != 0u;
-      rec[u] = a.fwd + (size_t)(ref >> 16) * 16u;
-      acc[u] = 0.0f;
-      max_len = max(max_len, len[u]);
+      doc[u] = doc_ref_of<VT>(a.fwd, live[u] ? a.doc_ref[st.id[idx[u]]] : 0ull);
     }
-    for (uint32_t e0 = l * 8u; e0 < max_len; e0 += 128u) {
-      DocChunk<CT, VT> d[kDivDocs];
-#pragma unroll
-      for (uint32_t u = 0; u < kDivDocs; ++u)
-        if (e0 < len[u]) load_pass<CT, VT>(d[u], rec[u], len[u], raw[u], e0);
-#pragma unroll
-      for (uint32_t u = 0; u < kDivDocs; ++u)
-        if (e0 < len[u]) {
-          uint32_t c[8];
-          if (Vt<VT>::sliced && raw[u]) {
-            raw_pass_components<CT, VT>(d[u], c);
-          } else {
-            slice_components<CT, VT>(d[u], c);
-          }
-          place_values<CT, VT>(d[u], raw[u]);
-          float w[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) w[i] = weight_of<DENSE>(smem, c[i], a.slot_bits);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) acc[u] = __fadd_rn(acc[u], __fmul_rn(w[i], slice_value<VT>(d[u].v, i)));
-        }
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < kDivDocs; ++u) {
-      float r = acc[u];
-      r = __fadd_rn(r, __shfl_xor(r, 8, 16));
-      r = __fadd_rn(r, __shfl_xor(r, 4, 16));
-      r = __fadd_rn(r, __shfl_xor(r, 2, 16));
-      r = __fadd_rn(r, __shfl_xor(r, 1, 16));
+    group_score<CT, VT, DENSE>(tab, doc, l, [&](uint32_t u, float score) {
       if (l == 0 && live[u]) {
         if (REL) {
-          st.rel[idx[u]] = r;
+          st.rel[idx[u]] = score;
         } else {
-          st.pen[idx[u]] = __float_as_uint(fmaxf(__uint_as_float(st.pen[idx[u]]), r));
+          st.pen[idx[u]] = __float_as_uint(fmaxf(__uint_as_float(st.pen[idx[u]]), score));
         }
       }
-    }
+    });
   }
 }
 
@@ -167,30 +113,23 @@ __global__ __launch_bounds__(kDiversifyBlock) void diversify_documents_kernel(Di
   __shared__ uint32_t s_pick[2];   // rel and pen bits of the selected entry
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   constexpr uint32_t nt = kDiversifyBlock;
-  const uint32_t slots = 1u << a.slot_bits;
   DivState st;
   st.id = (uint32_t*)(smem + a.table_bytes);
   st.rel = (float*)(st.id + a.cap);
   st.pen = (uint32_t*)(st.rel + a.cap);
   const uint32_t k = a.k;
 
-  if (DENSE) {
-    for (uint32_t i = tid; i <= a.dim; i += nt) ((float*)smem)[i] = 0.0f;
-  } else {
-    for (uint32_t i = tid; i < slots; i += nt) ((uint32_t*)smem)[i] = kHashEmpty;
-  }
+  const WeightTable tab = weight_table(smem, a.dim, a.slot_bits);
+  table_reset<DENSE>(tab, tid, nt);
   // the table's occupant (workgroup-uniform): none, a query or a document
   uint32_t occ = OCC_NONE, occ_q = 0;
   uint64_t occ_ref = 0;
   auto table_empty = [&]() {   // (the caller's barriers: nobody reads the table before, everybody sees it empty after)
     if (occ == OCC_NONE) return;
-    if (!DENSE) {
-      for (uint32_t i = tid; i < slots; i += nt) ((uint32_t*)smem)[i] = kHashEmpty;
-    } else if (occ == OCC_QUERY) {
-      const uint64_t p0 = a.q_off[occ_q], p1 = a.q_off[occ_q + 1];
-      for (uint64_t j = p0 + tid; j < p1; j += nt) ((float*)smem)[a.q_comp[j]] = 0.0f;
+    if (!DENSE || occ == OCC_QUERY) {
+      table_clear_query<DENSE>(tab, a, occ_q, tid, nt);
     } else {
-      table_walk_doc<CT, VT, DENSE, false>(a, smem, occ_ref);
+      workgroup_walk_doc<CT, VT>(a.fwd, occ_ref, kDivGroups, [&](uint32_t c, float) { table_put<DENSE>(tab, c, 0.0f); });
     }
     occ = OCC_NONE;
   };
@@ -205,23 +144,10 @@ __global__ __launch_bounds__(kDiversifyBlock) void diversify_documents_kernel(Di
       for (uint32_t i = tid; i < n; i += nt) st.id[i] = a.cand[c0 + i], st.pen[i] = 0u;
       __syncthreads();
       // phase 0: the query moves in, every entry's rel
-      const uint64_t b0 = a.q_off[q], b1 = a.q_off[q + 1];
-      for (uint64_t j = b0 + tid; j < b1; j += nt) {
-        const uint32_t c = a.q_comp[j];
-        const float w = Vt<VT>::half ? a.q_val[j] : __fmul_rn(a.q_val[j], a.val_scale);
-        if (DENSE) {
-          ((float*)smem)[c] = w;
-        } else {
-          uint32_t* keys = (uint32_t*)smem;
-          float* wts = (float*)(smem + (size_t)slots * 4u);
-          uint32_t slot = (c * 2654435761u) >> (32u - a.slot_bits);
-          while (atomicCAS(&keys[slot], kHashEmpty, c) != kHashEmpty) slot = (slot + 1u) & (slots - 1u);
-          wts[slot] = w;
-        }
-      }
+      table_fill_query<VT, DENSE>(tab, a, q, tid, nt);
       occ = OCC_QUERY, occ_q = q;
       __syncthreads();
-      stream_entries<CT, VT, DENSE, true>(a, smem, st, n);
+      stream_entries<CT, VT, DENSE, true>(a, tab, st, n);
       __syncthreads();
       // rounds
       for (uint32_t r = 0; r < k; ++r) {   // (left > 0 on entry: n > 0, and a round that leaves nothing ends the loop)
@@ -283,11 +209,15 @@ __global__ __launch_bounds__(kDiversifyBlock) void diversify_documents_kernel(Di
         table_empty();
         const uint64_t ref = a.doc_ref[sel];
         __syncthreads();   // the table is empty; s_best, s_left and s_pick were read
-        table_walk_doc<CT, VT, DENSE, true>(a, smem, ref);
+        // (the weight of an element: the f32 its stored bits stand for; fixed-u8: val_scale once for the value, once more
+        // as table_fill_query folds it into a query's weight)
+        workgroup_walk_doc<CT, VT>(a.fwd, ref, kDivGroups, [&](uint32_t c, float x) {
+          table_put<DENSE>(tab, c, Vt<VT>::half ? x : __fmul_rn(__fmul_rn(x, a.val_scale), a.val_scale));
+        });
         occ = OCC_DOC, occ_ref = ref;
         __syncthreads();
         // (d) the pen of what is left
-        stream_entries<CT, VT, DENSE, false>(a, smem, st, n);
+        stream_entries<CT, VT, DENSE, false>(a, tab, st, n);
         __syncthreads();
       }
     }
@@ -297,29 +227,115 @@ __global__ __launch_bounds__(kDiversifyBlock) void diversify_documents_kernel(Di
 
 using DiversifyKernel = void (*)(DiversifyArgs);
 DiversifyKernel diversify_kernel(uint32_t cw, uint32_t vt, bool dense) {
-  if (vt == SGPU_VAL_DOTVBYTE) return dense ? diversify_documents_kernel<2, VT_DVB, true> : diversify_documents_kernel<2, VT_DVB, false>;
-  if (vt == SGPU_VAL_FIXEDU8) {
-    if (cw == 2) return dense ? diversify_documents_kernel<2, VT_U8, true> : diversify_documents_kernel<2, VT_U8, false>;
-    return dense ? diversify_documents_kernel<4, VT_U8, true> : diversify_documents_kernel<4, VT_U8, false>;
+  return for_variant(cw, vt, dense, [](auto CW, auto VT, auto D) -> DiversifyKernel { return diversify_documents_kernel<CW(), VT(), D()>; });
+}
+
+// A diversify call: the kernel over the call's queries, a launch taking whole queries (next_whole_queries); the call's
+// rows - rerank's row buffers plus one for the penalties - stay on the device until its end, zeroed before the first
+// launch.
+sgpu_status diversify_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
+                          const float* vals, uint32_t nq, uint32_t max_nnz, uint32_t max_len, uint32_t max_cand, const uint64_t* cand_off,
+                          const uint64_t* cand_ids, float lambda, float mu, uint32_t k, const DiversifyOut& out) {
+  HIP_TRY(hipSetDevice(s->device));
+  CallStats& cs = s->diversify_stats;
+  cs.begin();
+  const LookupForm form = lookup_form(h, std::max(max_nnz, max_len));   // the hash table holds the longest query or candidate document
+  const uint32_t cap = std::max(64u, (max_cand + 63u) & ~63u);   // (<= 2048: 24 KiB of entry state)
+  const uint32_t lds = form.table_bytes + cap * 12u;
+  const DiversifyKernel kern = diversify_kernel(h.comp_width, h.value_type, form.dense);
+  int per_cu = 0;
+  sgpu_status st;
+  if ((st = kernel_fit(kern, kDiversifyBlock, lds, &per_cu)) != SGPU_OK) return st;
+  if (per_cu < 1) return fail(SGPU_ELIMIT, "the diversify kernel does not fit on a CU (%u bytes of LDS)", lds);
+  per_cu = std::min(per_cu, (int)(2048u / kDiversifyBlock));
+  const uint64_t max_grid = hooked_grid((uint64_t)s->n_cu * (uint32_t)per_cu, "SGPU_DIVERSIFY_GRID");
+  const uint64_t budget = launch_budget();
+
+  const uint64_t cells = (uint64_t)nq * k;
+  if ((st = stage_queries(s, q_off, comps, vals, nq, cand_off)) != SGPU_OK || (st = score_reserve(s, s->row_scores, cells * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->d_pen, cells * 4)) != SGPU_OK || (st = score_reserve(s, s->row_ids, cells * 8)) != SGPU_OK ||
+      (st = score_reserve(s, s->row_n, (uint64_t)nq * 4)) != SGPU_OK)
+    return st;
+  HIP_TRY(hipMemsetAsync(s->row_scores.p, 0, cells * 4, s->stream));
+  HIP_TRY(hipMemsetAsync(s->d_pen.p, 0, cells * 4, s->stream));
+  HIP_TRY(hipMemsetAsync(s->row_ids.p, 0, cells * 8, s->stream));
+  HIP_TRY(hipMemsetAsync(s->row_n.p, 0, (uint64_t)nq * 4, s->stream));
+  DiversifyArgs a{};
+  a.fwd = view.fwd;
+  a.doc_ref = view.doc_ref;
+  a.q_off = s->q_off.as<const uint64_t>();
+  a.q_comp = s->q_comp.as<const uint32_t>();
+  a.q_val = s->q_val.as<const float>();
+  a.cand_off = s->cand_off.as<const uint64_t>();
+  a.row_scores = s->row_scores.as<float>();
+  a.row_pen = s->d_pen.as<float>();
+  a.row_ids = s->row_ids.as<uint64_t>();
+  a.row_n = s->row_n.as<uint32_t>();
+  a.dim = (uint32_t)h.dim;
+  a.slot_bits = form.slot_bits;
+  a.table_bytes = form.table_bytes;
+  a.cap = cap;
+  a.k = k;
+  a.lambda = lambda;
+  a.mu = mu;
+  a.val_scale = h.val_scale;
+  cs.dense = form.dense;
+  cs.block = kDiversifyBlock;
+  cs.lds = lds;
+
+  for (uint32_t q = 0; q < nq;) {
+    const uint32_t qa = next_whole_queries(cand_off, nq, budget, &q);
+    const uint64_t first = cand_off[qa], n_cand = cand_off[q] - first;   // (<= max(budget, kDiversifyMaxCand) < 2^32)
+    if (n_cand == 0) continue;   // (queries without candidates: their rows are zero already)
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(q - qa, max_grid);
+    if ((st = stage_ids(s, cand_ids, first, n_cand)) != SGPU_OK) return st;
+    a.cand = s->cand.as<const uint32_t>();
+    a.cand_base = first;
+    a.q_first = qa;
+    a.q_last = q;
+    cs.grid = grid;
+    if ((st = launch_timed(s, kern, grid, kDiversifyBlock, lds, a)) != SGPU_OK || (st = launch_done(s, &cs)) != SGPU_OK) return st;
   }
-  if (cw == 2) return dense ? diversify_documents_kernel<2, VT_F16, true> : diversify_documents_kernel<2, VT_F16, false>;
-  return dense ? diversify_documents_kernel<4, VT_F16, true> : diversify_documents_kernel<4, VT_F16, false>;
+  HIP_TRY(hipMemcpyAsync(out.scores, s->row_scores.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out.penalties, s->d_pen.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out.doc_ids, s->row_ids.p, cells * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out.n, s->row_n.p, (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (uint32_t i = 0; i < nq; ++i) cs.extra[0] = std::max(cs.extra[0], (double)out.n[i]);
+  return SGPU_OK;
 }
 
 }  // namespace
 
-sgpu_status diversify_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t lds, int* per_cu) {
-  DiversifyKernel kern = diversify_kernel(cw, vt, dense);
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, (int)kDiversifyBlock, lds));
-  return SGPU_OK;
+sgpu_status diversify_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                       const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
+                                       float mu, uint32_t k, const DiversifyOut& out) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  uint32_t max_nnz = 0, max_len = 0, max_cand = 0;
+  const sgpu_status vst =
+      diversify_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, lambda, mu, k, out, &max_nnz, &max_len, &max_cand);
+  if (vst != SGPU_OK) return vst;
+  ScoreState* s = nullptr;
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
+  if (nq == 0) return SGPU_OK;
+  std::lock_guard<std::mutex> lk(s->mu);
+  try {
+    return diversify_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, max_nnz, max_len, max_cand,
+                         cand_off, cand_ids, lambda, mu, k, out);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
 }
 
-sgpu_status diversify_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t lds, hipStream_t stream,
-                                    const DiversifyArgs& a) {
-  hipLaunchKernelGGL(diversify_kernel(cw, vt, dense), dim3(grid), dim3(kDiversifyBlock), lds, stream, a);
-  HIP_TRY(hipGetLastError());
-  return SGPU_OK;
+// (test hook: what the last diversify call on `replica` measured - out8 = {device ms of its kernels, launches, grid of the last
+// launch, workgroup size, LDS bytes, 1 = dense table / 0 = hash, rounds of its longest query, 0}. tools/diversify_probe.py)
+bool diversify_debug_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  double v[8];
+  if (!call_stats_out(idx, replica, &ScoreState::diversify_stats, v)) return false;
+  const double d[8] = {v[0], v[1], v[3], (double)kDiversifyBlock, v[5], v[2], v[6], 0.0};   // (this hook's own slot order)
+  for (int i = 0; i < 8; ++i) out8[i] = d[i];
+  return true;
 }
 
 }  // namespace sgpu

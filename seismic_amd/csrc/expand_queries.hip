@@ -30,11 +30,35 @@
 
 #include <type_traits>
 
-#include "score_lookup.hpp"
+#include "score_state.hpp"
 
 namespace sgpu {
 
 namespace {
+
+constexpr uint32_t kExpandBlock = 1024;   // threads of a workgroup (16 wavefronts: the kernel's wave totals are sized by it)
+constexpr uint64_t kExpandTableBytes = 1ull << 30;   // most global scratch the tables of a launch's workgroups take
+
+struct ExpandArgs {
+  const uint8_t* fwd;         // DevView::fwd and doc_ref
+  const uint64_t* doc_ref;
+  const uint64_t* q_off;      // the call's staged queries and candidate offsets
+  const uint32_t* q_comp;
+  const float* q_val;
+  const uint64_t* cand_off;
+  const uint32_t* cand;       // the launch's candidate ids and weights: candidate i of the call at [i - cand_base]
+  const float* cand_w;
+  float* table;               // !DENSE: gridDim.x tables of dim + 1 floats (DENSE: the table is in LDS)
+  uint32_t* out_comps;        // the call's rows [nq x t] and counts
+  float* out_vals;
+  uint32_t* out_n;
+  uint64_t cand_base;
+  uint32_t q_first, q_last;   // the launch's queries [q_first, q_last)
+  uint32_t dim;
+  uint32_t t;
+  float alpha;
+  float val_scale;
+};
 
 constexpr uint32_t kExpandWaves = kExpandBlock / 64u;
 
@@ -164,28 +188,110 @@ __global__ __launch_bounds__(kExpandBlock) void expand_queries_kernel(ExpandArgs
 
 using ExpandKernel = void (*)(ExpandArgs);
 ExpandKernel expand_kernel(uint32_t cw, uint32_t vt, bool dense) {
-  if (vt == SGPU_VAL_DOTVBYTE) return dense ? expand_queries_kernel<2, VT_DVB, true> : expand_queries_kernel<2, VT_DVB, false>;
-  if (vt == SGPU_VAL_FIXEDU8) {
-    if (cw == 2) return dense ? expand_queries_kernel<2, VT_U8, true> : expand_queries_kernel<2, VT_U8, false>;
-    return dense ? expand_queries_kernel<4, VT_U8, true> : expand_queries_kernel<4, VT_U8, false>;
+  return for_variant(cw, vt, dense, [](auto CW, auto VT, auto D) -> ExpandKernel { return expand_queries_kernel<CW(), VT(), D()>; });
+}
+
+// An expand call: the kernel over the call's queries. A launch takes whole queries (next_whole_queries), so no table is
+// carried between launches; the call's rows stay on the device until its end.
+sgpu_status expand_run(ScoreState* s, const HostIndex& h, const DevView& view, const uint64_t* q_off, const uint32_t* comps,
+                       const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
+                       uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n) {
+  HIP_TRY(hipSetDevice(s->device));
+  CallStats& cs = s->expand_stats;
+  cs.begin();
+  // the table: in LDS where the dense form is chosen, else one per workgroup in the global scratch
+  const LookupForm form = lookup_form(h, 0);
+  const bool dense = form.dense;
+  const uint32_t lds = dense ? form.table_bytes : 0u;
+  const ExpandKernel kern = expand_kernel(h.comp_width, h.value_type, dense);
+  int per_cu = 0;
+  sgpu_status st;
+  if ((st = kernel_fit(kern, kExpandBlock, lds, &per_cu)) != SGPU_OK) return st;
+  if (per_cu < 1) return fail(SGPU_ELIMIT, "the expand kernel does not fit on a CU (%u bytes of LDS)", lds);
+  per_cu = std::min(per_cu, (int)(2048u / kExpandBlock));
+  uint64_t max_grid = (uint64_t)s->n_cu * (uint32_t)per_cu;
+  if (!dense) max_grid = std::max<uint64_t>(1, std::min<uint64_t>(max_grid, kExpandTableBytes / ((h.dim + 1) * 4)));
+  max_grid = hooked_grid(max_grid, "SGPU_EXPAND_GRID");
+  const uint64_t budget = launch_budget();
+
+  const uint64_t cells = (uint64_t)nq * t;
+  if ((st = stage_queries(s, q_off, comps, vals, nq, cand_off)) != SGPU_OK || (st = score_reserve(s, s->x_comps, cells * 4)) != SGPU_OK ||
+      (st = score_reserve(s, s->x_vals, cells * 4)) != SGPU_OK || (st = score_reserve(s, s->x_n, (uint64_t)nq * 4)) != SGPU_OK)
+    return st;
+  ExpandArgs a{};
+  a.fwd = view.fwd;
+  a.doc_ref = view.doc_ref;
+  a.q_off = s->q_off.as<const uint64_t>();
+  a.q_comp = s->q_comp.as<const uint32_t>();
+  a.q_val = s->q_val.as<const float>();
+  a.cand_off = s->cand_off.as<const uint64_t>();
+  a.out_comps = s->x_comps.as<uint32_t>();
+  a.out_vals = s->x_vals.as<float>();
+  a.out_n = s->x_n.as<uint32_t>();
+  a.dim = (uint32_t)h.dim;
+  a.t = t;
+  a.alpha = alpha;
+  a.val_scale = h.val_scale;
+  cs.dense = dense;
+  cs.block = kExpandBlock;
+  cs.lds = lds;
+
+  for (uint32_t q = 0; q < nq;) {
+    const uint32_t qa = next_whole_queries(cand_off, nq, budget, &q);
+    const uint64_t first = cand_off[qa], n_cand = cand_off[q] - first;   // (<= max(budget, kExpandMaxCand) < 2^32)
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(q - qa, max_grid);
+    if ((st = stage_ids(s, cand_ids, first, n_cand)) != SGPU_OK || (st = score_reserve(s, s->x_w, n_cand * 4)) != SGPU_OK) return st;
+    if (!dense) {
+      const uint64_t bytes = (uint64_t)grid * (h.dim + 1) * 4;
+      if ((st = score_reserve(s, s->x_table, bytes)) != SGPU_OK) return st;
+      cs.extra[0] = std::max(cs.extra[0], (double)bytes);
+    }
+    if (n_cand) HIP_TRY(hipMemcpyAsync(s->x_w.p, cand_w + first, n_cand * 4, hipMemcpyHostToDevice, s->stream));
+    a.cand = s->cand.as<const uint32_t>();
+    a.cand_w = s->x_w.as<const float>();
+    a.table = s->x_table.as<float>();
+    a.cand_base = first;
+    a.q_first = qa;
+    a.q_last = q;
+    cs.grid = grid;
+    if ((st = launch_timed(s, kern, grid, kExpandBlock, lds, a)) != SGPU_OK || (st = launch_done(s, &cs)) != SGPU_OK) return st;
   }
-  if (cw == 2) return dense ? expand_queries_kernel<2, VT_F16, true> : expand_queries_kernel<2, VT_F16, false>;
-  return dense ? expand_queries_kernel<4, VT_F16, true> : expand_queries_kernel<4, VT_F16, false>;
+  HIP_TRY(hipMemcpyAsync(out_comps, s->x_comps.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_vals, s->x_vals.p, cells * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_n, s->x_n.p, (uint64_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SGPU_OK;
 }
 
 }  // namespace
 
-sgpu_status expand_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t lds, int* per_cu) {
-  ExpandKernel kern = expand_kernel(cw, vt, dense);
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, (int)kExpandBlock, lds));
-  return SGPU_OK;
+sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
+                                  uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  uint32_t max_nnz = 0;
+  const sgpu_status vst =
+      expand_check_args(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha, t, out_comps, out_vals, out_n, &max_nnz);
+  if (vst != SGPU_OK) return vst;
+  ScoreState* s = nullptr;
+  const sgpu_status sst = score_state_of(idx, replica, &s);
+  if (sst != SGPU_OK) return sst;
+  if (nq == 0) return SGPU_OK;
+  std::lock_guard<std::mutex> lk(s->mu);
+  try {
+    return expand_run(s, idx->host, device_index_view(idx->replicas[replica]), q_off, comps, vals, nq, cand_off, cand_ids, cand_w, alpha,
+                      t, out_comps, out_vals, out_n);
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
 }
 
-sgpu_status expand_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t lds, hipStream_t stream, const ExpandArgs& a) {
-  hipLaunchKernelGGL(expand_kernel(cw, vt, dense), dim3(grid), dim3(kExpandBlock), lds, stream, a);
-  HIP_TRY(hipGetLastError());
-  return SGPU_OK;
+// (test hook: what the last expand call on `replica` measured - out8 = {device ms of its kernels, launches, 1 = table in LDS /
+// 0 = in global memory, grid of the last launch, workgroup size, LDS bytes, bytes of the global tables, 0}. tools/expand_probe.py)
+bool expand_debug_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  if (!call_stats_out(idx, replica, &ScoreState::expand_stats, out8)) return false;
+  out8[4] = (double)kExpandBlock;   // (a constant, also before the replica's first expand call)
+  return true;
 }
 
 }  // namespace sgpu

@@ -38,25 +38,6 @@ namespace sgpu {
 
 namespace {
 
-__device__ __forceinline__ uint64_t group_max(uint64_t v) {
-#pragma unroll
-  for (int s = 8; s >= 1; s >>= 1) {
-    const uint64_t o = __shfl_xor(v, s, 16);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t group_or(uint32_t v) {
-#pragma unroll
-  for (int s = 8; s >= 1; s >>= 1) v |= __shfl_xor(v, s, 16);
-  return v;
-}
-__device__ __forceinline__ uint32_t group_sum(uint32_t v) {
-#pragma unroll
-  for (int s = 8; s >= 1; s >>= 1) v += __shfl_xor(v, s, 16);
-  return v;
-}
-
 template <int CW, int VT, bool DENSE>
 __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) {
   using CT = typename std::conditional<CW == 2, uint16_t, uint32_t>::type;
@@ -65,6 +46,9 @@ __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) 
   const uint32_t ng = nt >> 4, g = tid >> 4, l = tid & 15u;
   const uint32_t slots = 1u << a.slot_bits;
   const uint32_t m = a.m;
+  // (the table's block and the ref's decode are written out, as in the parent: through table_fill_query / table_clear_query
+  // and doc_ref_of six of this kernel's ten variants compile to other code; the lookup and the reductions are shared)
+  const WeightTable tab = weight_table(smem, a.dim, a.slot_bits);
   // the weight table: built, used and cleared as in score_documents_kernel
   if (DENSE) {
     for (uint32_t i = tid; i <= a.dim; i += nt) ((float*)smem)[i] = 0.0f;
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) 
           place_values<CT, VT>(d, raw);
           float w[8];
 #pragma unroll
-          for (int i = 0; i < 8; ++i) w[i] = weight_of<DENSE>(smem, c[i], a.slot_bits);
+          for (int i = 0; i < 8; ++i) w[i] = weight_of<DENSE>(tab, c[i]);
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             const float x = slice_value<VT>(d.v, i);
@@ -146,7 +130,7 @@ __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) 
             }
           }
         }
-        found = group_sum(found);
+        found = group16_sum(found);
         n_terms += found;
         if (found == 0) continue;
         k[8] = lk[0], v[8] = lv[0], k[9] = lk[1], v[9] = lv[1];
@@ -158,12 +142,12 @@ __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) 
 #pragma unroll
           for (int i = 1; i < 10; ++i)
             if (k[i] > bk) bk = k[i], bv = v[i];
-          const uint64_t gk = group_max(bk);
+          const uint64_t gk = group16_max(bk);
           if (gk == 0) break;   // no key is left
           // (exactly one lane: a pair's keys are distinct because a document's components are strictly ascending -
           // validate_desc in host_index.cpp and build_host_index in builder.cpp refuse anything else)
           const bool mine = bk == gk;
-          const uint32_t gv = group_or(mine ? bv : 0u);
+          const uint32_t gv = group16_or(mine ? bv : 0u);
           if (mine) {
 #pragma unroll
             for (int i = 0; i < 10; ++i)
@@ -178,11 +162,7 @@ __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) 
           }
         }
       }
-      float s = acc;
-      s = __fadd_rn(s, __shfl_xor(s, 8, 16));
-      s = __fadd_rn(s, __shfl_xor(s, 4, 16));
-      s = __fadd_rn(s, __shfl_xor(s, 2, 16));
-      s = __fadd_rn(s, __shfl_xor(s, 1, 16));
+      const float s = group16_sum(acc);
       if (!live) continue;
       const size_t at = (size_t)tile.y + idx;
       if (l == 0) {
@@ -218,31 +198,10 @@ __global__ __launch_bounds__(1024) void explain_documents_kernel(ExplainArgs a) 
   }
 }
 
-using ExplainKernel = void (*)(ExplainArgs);
-ExplainKernel explain_kernel(uint32_t cw, uint32_t vt, bool dense) {
-  if (vt == SGPU_VAL_DOTVBYTE) return dense ? explain_documents_kernel<2, VT_DVB, true> : explain_documents_kernel<2, VT_DVB, false>;
-  if (vt == SGPU_VAL_FIXEDU8) {
-    if (cw == 2) return dense ? explain_documents_kernel<2, VT_U8, true> : explain_documents_kernel<2, VT_U8, false>;
-    return dense ? explain_documents_kernel<4, VT_U8, true> : explain_documents_kernel<4, VT_U8, false>;
-  }
-  if (cw == 2) return dense ? explain_documents_kernel<2, VT_F16, true> : explain_documents_kernel<2, VT_F16, false>;
-  return dense ? explain_documents_kernel<4, VT_F16, true> : explain_documents_kernel<4, VT_F16, false>;
-}
-
 }  // namespace
 
-sgpu_status explain_kernel_fit(uint32_t cw, uint32_t vt, bool dense, uint32_t block, uint32_t lds, int* per_cu) {
-  ExplainKernel kern = explain_kernel(cw, vt, dense);
-  HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, (int)block, lds));
-  return SGPU_OK;
-}
-
-sgpu_status explain_kernel_launch(uint32_t cw, uint32_t vt, bool dense, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t stream,
-                                  const ExplainArgs& a) {
-  hipLaunchKernelGGL(explain_kernel(cw, vt, dense), dim3(grid), dim3(block), lds, stream, a);
-  HIP_TRY(hipGetLastError());
-  return SGPU_OK;
+ExplainKernel explain_kernel(uint32_t cw, uint32_t vt, bool dense) {
+  return for_variant(cw, vt, dense, [](auto CW, auto VT, auto D) -> ExplainKernel { return explain_documents_kernel<CW(), VT(), D()>; });
 }
 
 }  // namespace sgpu

@@ -11,7 +11,7 @@ namespace sgpu {
 
 struct DeviceIndex;  // search.hip
 struct ExactFile;    // exact_device.hip
-struct ScoreState;   // score_documents.hip
+struct ScoreState;   // score_state.hpp
 
 struct HostIndex {
   uint32_t comp_width = 2;
@@ -149,7 +149,7 @@ sgpu_status diversify_check_args(const HostIndex& h, const uint64_t* q_off, cons
 sgpu_status diversify_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                      const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
                                      uint32_t num_threads, const DiversifyOut& out);
-// score_documents.hip
+// score_documents.hip (the state itself: score_state.hpp)
 void score_state_free(ScoreState* s);
 
 // filter.hip: which filter a launch searches with (f null: none) and on which replica of the index

@@ -3,7 +3,10 @@
 (mnemonics and operands, no addresses). A PMC traffic figure recorded in profiles/pmc_traffic.json belongs to the machine
 code it was measured on; an edit elsewhere in search_kernel.inc (another template instantiation) changes the source id of
 the file but not that code - bench.py accepts a recorded figure when either matches.
-usage: kernel_code_id.py [library] [regex over demangled names]   -> one line per symbol"""
+usage: kernel_code_id.py [library] [regex over demangled names] [kernel name]   -> one line per symbol
+The kernel name (default seismic_search_kernel) picks the function template whose instances are looked at; the library
+may also be a bare code object (hipcc --offload-device-only --no-gpu-bundle-output), which needs no link:
+  kernel_code_id.py build/score_documents.co "" score_documents_kernel"""
 import hashlib
 import os
 import re
@@ -15,16 +18,18 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import check_coop_asm as cca  # noqa: E402
 
 
-def code_ids(lib=None, pattern=r"seismic_search_kernel<"):
-    """{demangled symbol (template arguments only): 16 hex digits} for the search-kernel symbols matching `pattern`."""
+def code_ids(lib=None, pattern=None, kernel="seismic_search_kernel"):
+    """{demangled symbol (template arguments only; "" for a kernel that is no template): 16 hex digits} for the symbols of
+    `kernel` in namespace sgpu (or an unnamed one inside it) whose demangled name matches `pattern`."""
     lib = lib or os.environ.get("SGPU_LIB") or os.path.join(cca.ROOT, "seismic_amd", "libseismic_hip.so")
-    rx, out = re.compile(pattern), {}
+    rx, out = re.compile(pattern or (kernel + r"\b")), {}
+    mangled = re.compile(r"^_ZN4sgpu(?:12_GLOBAL__N_1)?%d%s" % (len(kernel), kernel))
     with tempfile.TemporaryDirectory() as td:
-        for k, co in enumerate(cca.code_objects(lib)):
+        for k, co in enumerate(cca.code_objects(lib) or [open(lib, "rb").read()]):
             path = os.path.join(td, "co%d.o" % k)
             open(path, "wb").write(co)
             syms = subprocess.run([cca.LLVM + "/llvm-readelf", "-s", "-W", path], capture_output=True, text=True).stdout.split("\n")
-            names = sorted({l.split()[-1] for l in syms if l.strip() and " FUNC " in l and l.split()[-1].startswith("_ZN4sgpu21seismic_search_kernel")})
+            names = sorted({l.split()[-1] for l in syms if l.strip() and " FUNC " in l and mangled.match(l.split()[-1])})
             if not names:
                 continue
             dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
@@ -43,11 +48,12 @@ def code_ids(lib=None, pattern=r"seismic_search_kernel<"):
                     h[cur].update((l.split("//")[0].strip() + "\n").encode())
             for m, d in pick:
                 if m in h:
-                    out[re.search(r"seismic_search_kernel(<.*?>)\(", d).group(1)] = h[m].hexdigest()[:16]
+                    out[re.search(kernel + r"(<.*?>)?\(", d).group(1) or ""] = h[m].hexdigest()[:16]
     return out
 
 
 if __name__ == "__main__":
-    ids = code_ids(sys.argv[1] if len(sys.argv) > 1 else None, sys.argv[2] if len(sys.argv) > 2 else r"seismic_search_kernel<")
+    ids = code_ids(sys.argv[1] if len(sys.argv) > 1 else None, sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] else None,
+                   sys.argv[3] if len(sys.argv) > 3 else "seismic_search_kernel")
     for k in sorted(ids):
         print(ids[k], k)
