@@ -287,7 +287,7 @@ sgpu_status device_index_upload(const HostIndex& h, int device, DeviceIndex** ou
       d->view.row_dir_buckets = 0;
       if (cw == 2) {
         // u16 components: the hashed row directory IS the row index on the device - a query component's summary row
-        // {first entry, entries, split point} in one trip (search_kernel.inc: build_row_table); the CSR arrays the
+        // {first entry, entries, split point} in one trip (search_stage01.inc: build_row_table); the CSR arrays the
         // binary search of the u32 kernels walks (row_comp, row_ptr, row_mid, list_row_start: 1.7 GB for the 8.8M-document
         // index) are not uploaded at all.
         std::vector<uint32_t> dir;

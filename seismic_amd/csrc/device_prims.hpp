@@ -14,7 +14,7 @@ SGPU_DEV uint32_t ordered_u32(float x) {
 }
 SGPU_DEV float ordered_u32_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
-// Inclusive prefix sum over the 64 lanes of a wavefront, by shuffles (search_kernel.inc has its own DPP form).
+// Inclusive prefix sum over the 64 lanes of a wavefront, by shuffles (search_lds.inc has its own DPP form).
 SGPU_DEV uint32_t wave_incl_scan(uint32_t v) {
   const uint32_t lane = __lane_id();
 #pragma unroll

@@ -92,7 +92,7 @@ SGPU_HD inline uint32_t hash_slot(uint32_t c, uint32_t mult) {   // top bits of 
   return (uint32_t)(((uint64_t)(c & 0xffffffu) * mult) & 0xffffffffull) >> (32 - kHashBits);
 }
 enum { STATS_WORDS = 24 };
-enum { kStateWords = 160 };   // per-workgroup state words in LDS (ST_* in search_kernel.inc)   // per-query stats: 8 work counters + 12 phase clocks (>>4) + slot + pad
+enum { kStateWords = 160 };   // per-workgroup state words in LDS (ST_* in search_lds.inc)   // per-query stats: 8 work counters + 12 phase clocks (>>4) + slot + pad
 
 // Cooperative mode (small launches, launch tails): workgroups that find the query queue empty do not
 // exit but HELP the workgroups that still own a query. An owner whose heap is full publishes one WIDE
@@ -103,7 +103,7 @@ enum { kStateWords = 160 };   // per-workgroup state words in LDS (ST_* in searc
 // traversal order with the reference's sequential rules (live threshold, block decided at its first
 // item, heap membership for re-encountered documents). Scores do not depend on who computes them and a
 // staler threshold only admits more blocks, so the result is the reference's, bit for bit.
-// All shared words are written and read with agent-scope (sc1) accesses; see search_kernel.inc.
+// All shared words are written and read with agent-scope (sc1) accesses; see search_coop.inc.
 struct CoopView {
   uint64_t* open;       // [8] bit s: slot s has an open round with unclaimed positions (one 64-byte line)
   uint32_t* counters;   // [0] idle workgroups [1] finished queries [2] exited workgroups [3] sticky protocol-error code
@@ -111,7 +111,7 @@ struct CoopView {
                         //   words of another round than the claimed one); the host reads it after every cooperative launch
   uint64_t* slots;      // per owner slot (blockIdx.x), kCoopSlotWords u64:
                         //   [0] claim = next chunk:20 | positions of the round:22 | positions per chunk:10 | round:10
-                        //       (search_kernel.inc: co_claim_word; claimed with fetch_add(1) - round-independent)
+                        //       (search_coop.inc: co_claim_word; claimed with fetch_add(1) - round-independent)
                         //   [1] done:32 (positions reported)   [2] n_cand:32   [3] query:32 | thr0:32   [4] cut:32 | round:32
                         // Invariant between launches: open[] and counters[0..2] are zero (the last workgroup out
                         // re-zeroes them and the slot words). Nothing else of the board needs to be: a slot's words
@@ -150,7 +150,7 @@ struct KParams {
   uint32_t queue_base;   // value of the work counter when the launch starts (0 when the counter is zeroed per launch;
                          // latency-bound calls let it run on: a launch of nq queries on a grid of G workgroups takes
                          // exactly nq + G tickets, so the host knows where the next launch begins - no reset to enqueue)
-  uint32_t ring;         // streamed stage 2 (r06; search_kernel.inc "stage 2 as a stream"): item slots of the ring in
+  uint32_t ring;         // streamed stage 2 (r06; search_stream.inc "stage 2 as a stream"): item slots of the ring in
                          // LDS, a power of two >= 256 (stream_ring_bytes of them fit the union region); 0 = the round loop
 };
 
@@ -164,7 +164,7 @@ enum { kStreamFeedPos = SGPU_STREAM_FEED_POS };   // positions per step of the f
 SGPU_HD_EARLY inline uint32_t stream_ring_bytes(uint32_t ring) { return ring * 18u + ring / 16u + (uint32_t)kStreamFeedPos * 10u; }
 
 // The scoring loop's weights (q_sc, preceded by the 0.0 slot) sit at a FIXED offset of the dynamic LDS, so that the
-// scaled-byte dense lookup (search_kernel.inc: kScaledMaxNnz) can address them as `byte + constant`.
+// scaled-byte dense lookup (search_lds.inc: kScaledMaxNnz) can address them as `byte + constant`.
 enum { kQscOffset = 0 };
 struct LdsLayout {   // byte offsets into dynamic LDS, all multiples of 16
   uint32_t q_comp, q_val, q_sc, q_bits, q_rank, sel, rt_start, rt_mid, rt_pre, dots, order, uni, part, heap, st;

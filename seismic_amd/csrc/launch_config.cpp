@@ -141,7 +141,7 @@ sgpu_status launch_configure(const LaunchInput& in, LaunchConfig* out) {
   const bool coop_force = kn.coop_mode == 2;
   const bool coop = plain_search && kn.coop_mode != 1 && !in.coop_broken && (coop_force || coop_by_size(in)) &&
                     variant_built(NT, kr, false, true);
-  // Streamed stage 2 (r06, search_kernel.inc "stage 2 as a stream"): plain search launches (the cooperative variant - small
+  // Streamed stage 2 (r06, search_stream.inc "stage 2 as a stream"): plain search launches (the cooperative variant - small
   // launches - and the counted pass keep the round loop). Its union region holds a RING of item slots, a power of two: the
   // fitting loops below step `items` down by 128 as they always did; for a streamed launch 1024 items mean a ring of 1024
   // slots (20.4 KB where the round loop's tables of 1024 items take 22.5), anything from 512 on one of 512, less 256.

@@ -13,7 +13,7 @@ static inline uint32_t row_dir_bucket_host(uint32_t key, uint32_t n_buckets) {  
   return (uint32_t)(((uint64_t)(uint32_t)(key * 2654435761u) * n_buckets) >> 32);
 }
 
-// ---- compressed component stream (SGPU_VAL_DOTVBYTE: search_kernel.inc VT_DVB) -----------------------------------
+// ---- compressed component stream (SGPU_VAL_DOTVBYTE: record.hpp VT_DVB) -----------------------------------
 // A document is stored as 12-byte slices of eight elements - the slice's first component in 16 bits, the gaps of
 // elements 1 .. 3 in 12 bits each, those of elements 4 .. 7 in 11 bits each - when every gap fits its field; otherwise
 // it keeps the raw record form and its refs carry kDvbRawBit in the length field. `raw` is EMPTY for an index that is

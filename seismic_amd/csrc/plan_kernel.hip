@@ -22,7 +22,7 @@
 // starts in this one's tail (profiles/r06_entry_point_final.txt).
 // The LDS layout itself is sized on the host from the maxima of EARLIER chunks on the same index and query_cut (they
 // travel back with the rows); a query that needs more block dots than that walks its lists in groups - slower for that
-// query, identical results (search_kernel.inc: plan_list_group).
+// query, identical results (search_stage01.inc: plan_list_group).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -166,7 +166,7 @@ SGPU_DEV void place_values(DocChunk<CT, VT>& d, bool raw) {
 
 // Value i (0 .. 7) of a slice whose values are in place (place_values), as the f32 the stored bits stand for (fixed-u8: the
 // code itself - its power-of-two scale is folded into the weights). Used by score_documents_kernel only: the search
-// kernels multiply straight from the stored bits (search_kernel.inc: mul_val).
+// kernels multiply straight from the stored bits (search_score.inc: mul_val).
 template <int VT>
 SGPU_DEV float slice_value(const uint4& val, int i) {
   const uint32_t v[4] = {val.x, val.y, val.z, val.w};

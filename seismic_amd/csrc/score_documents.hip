@@ -1,7 +1,7 @@
 // score_documents.hip — scores of caller-given documents on the device (sgpu_score_documents), and the launcher that
 // sgpu_rerank_documents and sgpu_explain_documents run through as well.
 //
-// A score is what the search kernels return for the document (search_kernel.inc: score_class), bit for bit: the full
+// A score is what the search kernels return for the document (search_score.inc: score_class), bit for bit: the full
 // query's dot product over the document's stored values in the canonical order - 16 accumulators, element e goes to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply
 // then add, each rounded once. Components the query does not carry resolve to the weight 0.0 and are added as +-0.0,

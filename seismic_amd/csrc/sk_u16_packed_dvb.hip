@@ -1,5 +1,5 @@
 // sk_u16_packed_dvb.hip — the search kernel family for uint16_t components with the LK_PACKED query lookup table,
-// DotVByte forward index: fixed-u8 codes + eight 12-bit component gaps per slice (search_kernel.inc: VT_DVB).
+// DotVByte forward index: fixed-u8 codes + eight 12-bit component gaps per slice (record.hpp: VT_DVB).
 #include "search_kernel.inc"
 
 namespace sgpu {

@@ -570,7 +570,7 @@ def test_hashed_row_directory_finds_every_summary_row_and_nothing_else():
     """DevView::row_dir (r05): stage 1 finds the summary row of (posting list, query component) in the bucket
     row_dir_bucket(list << 16 | component) - or a following one - of a table of 4-slot buckets. Every row of the index must be
     found with its {first entry, entries, split point}, absent pairs must end on an empty slot, and the table is at
-    most 60 % full. The lookup below restates the kernel's (search_kernel.inc: build_row_table)."""
+    most 60 % full. The lookup below restates the kernel's (search_stage01.inc: build_row_table)."""
     dim = 3000
     off, comps, vals = random_dataset(5, 20000, dim, nnz_lo=8, nnz_hi=120)
     ix = _native.NativeIndex.build(2, dim, off, comps, vals, BuildConfig.defaults(n_postings=300, centroid_fraction=0.2))

@@ -41,3 +41,21 @@ def test_recorded_traffic_is_keyed_by_the_machine_code_it_was_measured_on():
             assert got == float(e["traffic_bytes"])
         else:   # the kernel was edited since: no figure, and the line says why
             assert got is None and e["symbol_code_id"] in note
+
+
+def test_the_source_id_the_tools_record_covers_every_part_of_the_kernel():
+    """bench.kernel_source_id() hashes search_kernel.inc, device_types.hpp and the sk_*.hip units; the kernel's text lies in
+    the search_*.inc parts that search_kernel.inc includes. tools/record_profile.py therefore records
+    kernel_code_id.kernel_source_id_full(), over every file the kernel is compiled from - an id bench's source comparison
+    cannot match, so a recorded figure is accepted on its machine code alone. A part nobody includes fails here."""
+    import glob
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import bench
+    import kernel_code_id
+    files = kernel_code_id.kernel_source_files()
+    parts = sorted(os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "seismic_amd", "csrc", "search_*.inc")))
+    assert len(parts) > 1, parts   # search_kernel.inc and its parts
+    for f in ["search_kernel.inc", "device_types.hpp", "record.hpp"] + parts:
+        assert f in files, (f, files)
+    assert kernel_code_id.kernel_source_id_full() != bench.kernel_source_id()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tripwire for the cooperative kernel variant's machine code (VERDICT r03 "weak" #3).
 
-The cooperative protocol (search_kernel.inc: coop_work / wide_round / coop_help) orders its publishes with
+The cooperative protocol (search_coop.inc: coop_work / wide_round / coop_help) orders its publishes with
 `s_waitcnt vmcnt(0)` in every storing wave + a workgroup barrier + ONE relaxed agent-scope store, and its source keeps
 every thread-0 section between two barriers because ROCm 7.2 was seen fusing adjacent ones and breaking the pairing of
 barriers. Neither is something the HIP memory model or the compiler promises to keep. This tool disassembles the

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Experiment builds of the product library: only the named kernel families are recompiled (with extra flags and / or a
-# patched copy of search_kernel.inc); every other object is taken from the default build. The result is
+# patched copy of search_kernel.inc - its search_*.inc parts are taken from csrc); every other object is taken from the default build. The result is
 # seismic_amd/libseismic_hip_<name>.so (run with SGPU_LIB=<path>). Nothing of this ships in the default library.
 #   tools/exp_build.sh <name> "<extra hipcc flags>" [patched search_kernel.inc] [unit ...]   (default unit: sk_u16_dense)
 set -e

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Identity of a kernel symbol's MACHINE CODE in a built library: sha256 over the symbol's disassembled instructions
 (mnemonics and operands, no addresses). A PMC traffic figure recorded in profiles/pmc_traffic.json belongs to the machine
-code it was measured on; an edit elsewhere in search_kernel.inc (another template instantiation) changes the source id of
-the file but not that code - bench.py accepts a recorded figure when either matches.
+code it was measured on; an edit elsewhere in the kernel's source (another template instantiation) changes the source id
+but not that code - bench.py accepts a recorded figure when either matches. kernel_source_files() / kernel_source_id_full():
+the kernel's source over ALL its files (search_kernel.inc's parts included), which is what the tools record.
 usage: kernel_code_id.py [library] [regex over demangled names] [kernel name]   -> one line per symbol
 The kernel name (default seismic_search_kernel) picks the function template whose instances are looked at; the library
 may also be a bare code object (hipcc --offload-device-only --no-gpu-bundle-output), which needs no link:
@@ -50,6 +51,36 @@ def code_ids(lib=None, pattern=None, kernel="seismic_search_kernel"):
                 if m in h:
                     out[re.search(kernel + r"(<.*?>)?\(", d).group(1) or ""] = h[m].hexdigest()[:16]
     return out
+
+
+CSRC = os.path.join(cca.ROOT, "seismic_amd", "csrc")
+
+
+def kernel_source_files():
+    """Base names of the csrc files the search kernels are compiled from: the set bench.kernel_source_id() hashes
+    (search_kernel.inc, device_types.hpp, sk_*.hip) and every csrc file search_kernel.inc includes in quotes, transitively
+    (its search_*.inc parts, record.hpp, ...), sorted."""
+    todo = ["search_kernel.inc", "device_types.hpp"] + [f for f in os.listdir(CSRC) if re.fullmatch(r"sk_\w+\.hip", f)]
+    seen = set()
+    while todo:
+        f = todo.pop()
+        if f in seen or not os.path.exists(os.path.join(CSRC, f)):
+            continue
+        seen.add(f)
+        if f.startswith("sk_"):   # (the units only include search_kernel.inc)
+            continue
+        todo += re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(CSRC, f)).read(), re.M)
+    return sorted(seen)
+
+
+def kernel_source_id_full():
+    """Identity of the search kernels' whole source. bench.kernel_source_id() covers search_kernel.inc, device_types.hpp and
+    the units only: an edit to an included part leaves it as it was. New entries of profiles/pmc_traffic.json carry this id
+    instead, which bench's source comparison never matches - its machine-code comparison (symbol_code_id) decides."""
+    h = hashlib.sha256()
+    for f in kernel_source_files():
+        h.update(f.encode() + b"\0" + open(os.path.join(CSRC, f), "rb").read())
+    return h.hexdigest()[:16]
 
 
 if __name__ == "__main__":

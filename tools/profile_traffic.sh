@@ -14,9 +14,11 @@ for C in FETCH_SIZE WRITE_SIZE; do
 done
 python "$REPO/tools/pmc_summary.py" "$OUT" > "$OUT/summary.json"
 find "$OUT" -name "*.db" -delete; find "$OUT" -type f -size +400k -delete   # (gpurun copies at most 64 MiB back: summaries only)
-python - "$OUT" <<'PY'
-import json, sys
+python - "$OUT" "$REPO" <<'PY'
+import json, os, sys
 out = sys.argv[1]
+sys.path.insert(0, os.path.join(sys.argv[2], "tools"))
+import kernel_code_id
 s = json.load(open(out + "/summary.json"))
 line = json.loads(open(out + "/pmc_FETCH_SIZE.json").read().strip().splitlines()[-1])
 def counter(tag, name):
@@ -29,7 +31,7 @@ def counter(tag, name):
 f, w = counter("pmc_FETCH_SIZE", "FETCH_SIZE"), counter("pmc_WRITE_SIZE", "WRITE_SIZE")
 ent = {"traffic_bytes": int(2 * f["mean"] * 1024 + w["mean"] * 1024), "fetch_size_kib": int(f["mean"]),
        "write_size_kib": int(w["mean"]), "dispatches": f["dispatches"],
-       "kernel_source_id": line["roofline"]["kernel_source_id"],   # bench.py reports the figure only for this kernel source
+       "kernel_source_id": kernel_code_id.kernel_source_id_full(),   # every file of the kernel (tools/record_profile.py)
        "algorithmic_bytes": json.loads(open(out + "/trace_bench.json").read().strip().splitlines()[-1])["roofline"]["algorithmic_bytes_per_launch"]}
 ent["ratio"] = round(ent["traffic_bytes"] / ent["algorithmic_bytes"], 4) if ent["algorithmic_bytes"] else None
 print(json.dumps({line["config"]["workload_key"]: ent}, indent=1))

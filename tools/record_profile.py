@@ -5,6 +5,8 @@ measured HBM traffic in profiles/pmc_traffic.json under the workload AND the ker
   python tools/record_profile.py traffic gpurun_out/r03_traffic_c5 r03_traffic_c5"""
 import json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_code_id  # noqa: E402
 mode, src, tag = sys.argv[1], os.path.join(ROOT, sys.argv[2]), sys.argv[3]
 P = os.path.join(ROOT, "profiles")
 s = json.load(open(os.path.join(src, "summary.json")))
@@ -30,15 +32,16 @@ def timed_kernel(table):
 K = timed_kernel(s["counters"]["pmc_FETCH_SIZE"])
 f, w = s["counters"]["pmc_FETCH_SIZE"][K]["FETCH_SIZE"], s["counters"]["pmc_WRITE_SIZE"][K]["WRITE_SIZE"]
 ent = {"traffic_bytes": int(2 * f["mean"] * 1024 + w["mean"] * 1024), "fetch_size_kib": int(f["mean"]), "write_size_kib": int(w["mean"]),
-       "dispatches": f["dispatches"], "kernel_source_id": pmc_line["roofline"]["kernel_source_id"],
+       # the id over ALL the kernel's source files (the tree that ran travels with the library). It is not the id bench.py
+       # computes - that one leaves out search_kernel.inc's parts -, so bench never accepts this entry on source alone: its
+       # comparison of the symbol's machine code (below) decides
+       "dispatches": f["dispatches"], "kernel_source_id": kernel_code_id.kernel_source_id_full(),
        "algorithmic_bytes": line["roofline"]["algorithmic_bytes_per_launch"]}
 ent["ratio"] = round(ent["traffic_bytes"] / ent["algorithmic_bytes"], 4) if ent["algorithmic_bytes"] else None
 # the symbol the counter passes ran and the identity of its machine code in the library of this tree (the one that ran:
 # the .so travels to the GPU box with the snapshot) - bench.py reports the figure for that code only
 ent["symbol"] = K
 try:
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_code_id
     ent["symbol_code_id"] = kernel_code_id.code_ids(None, r"seismic_search_kernel<").get(K.replace("seismic_search_kernel", ""))
 except Exception as e:   # noqa: BLE001
     print("record_profile: no machine-code id (%r)" % (e,), file=sys.stderr)
