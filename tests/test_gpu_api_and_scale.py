@@ -71,7 +71,12 @@ def test_golden_synth_small_on_gpu():
     dict(SGPU_FWD_LAYOUT="doc"),                                                              # one record per document
     dict(SGPU_FWD_LAYOUT="doc", SGPU_REC_LINE="16"),
 ])
-def test_kernel_paths_under_forced_small_buffers(env, monkeypatch):
+# (launches of 48 queries are cooperative ones by default - the round loop; "plain" switches that variant off, so the same
+# knob sets also run stage 2 as a stream)
+@pytest.mark.parametrize("variant", ["default", "plain"])
+def test_kernel_paths_under_forced_small_buffers(env, variant, monkeypatch):
+    if variant == "plain":
+        monkeypatch.setenv("SGPU_COOP", "0")
     for k_, v_ in env.items():
         monkeypatch.setenv(k_, v_)
     dim = 300
