@@ -582,6 +582,58 @@ sgpu_status sgpu_diversify_documents_host(const sgpu_index* idx,
     float lambda, float mu, uint32_t k, uint32_t num_threads,
     float* out_scores, float* out_penalties, uint64_t* out_doc_ids, uint32_t* out_n);
 
+/* ---- collapse: the k best groups of a query's candidates ----------------------
+ * Field collapsing on the device: the candidates carry a group key each (the document a passage belongs to, a site, an
+ * author, a product), and what comes back per query is its k best GROUPS, each scored by its best member (m = 1: MaxP)
+ * or by the sum of its m best members. The reference has no counterpart. Queries and candidates are given exactly as for
+ * sgpu_score_documents (any order, repeats allowed, possibly none); cand_groups[i] is the group key of entry i: any u32,
+ * 0 and 0xffffffff included. The caller owns its meaning: the library keeps no per-document state, and the call adds no
+ * index array.
+ * Members. The members of group g for query q are the DISTINCT pairs (g, document id) among q's entries: a pair listed
+ * twice counts once, the same id listed under two keys is a member of both groups. No consistency check is made, and none
+ * is needed. A member's score is, bit for bit, what sgpu_score_documents returns for (q, id). The members of a group are
+ * ordered by score descending, then id ascending; the first is the group's BEST MEMBER.
+ * Group score. The f32 sum of the group's first min(m, members) members, added in that order, starting from the best
+ * member's score: s = score[0]; s = fl(s + score[1]); ... - never reassociated, never widened. m = 1 is MaxP; m >= the
+ * group's size is the sum over all of them. A group score is never -0.0, because no member score is (sgpu_rerank_documents
+ * says why, and x + y is -0.0 only if both are): the ordered integer image of the bits orders finite group scores
+ * numerically, and the device selects on it.
+ * Rows. Row q of the nq x k row-major outputs holds q's groups ordered by group score descending, then group key
+ * ascending, cut to k: out_groups the key, out_scores the group score, out_best_ids and out_best_scores the best
+ * member's id and score, out_members the number of members (all of them, not min(m, .)). out_n[q] = min(k, groups of q).
+ * Slots past out_n[q] are zero in all five arrays; a query without candidates gets out_n = 0 and zeroed rows. An empty
+ * query scores every member +0.0, so its groups come in key order.
+ * Consequences. With m = 1 and every entry's key equal to its (u32) document id, out_best_ids, out_scores and out_n are
+ * exactly the rows of sgpu_rerank_documents. The rows do not depend on the order in which the candidates are listed, nor
+ * on how the call is cut into launches. Rows that contain a score that is not finite need not match the host twin
+ * (sgpu_score_documents makes the same reservation).
+ * Checks, in this order: null arguments (SGPU_EINVAL; cand_ids, cand_groups and the six outputs too, also when there is
+ * nothing to do), everything sgpu_score_documents checks in its order, a query with more than 4096 listed candidates
+ * (SGPU_ELIMIT; the message names the query), m == 0 (SGPU_EINVAL), m > 64 (SGPU_ELIMIT), k == 0 (SGPU_EINVAL), k > 1024
+ * (SGPU_ELIMIT), index not uploaded or replica out of range (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays
+ * usable). nq == 0 is SGPU_OK.
+ * Limits. A query's entries are sorted three times by one workgroup without leaving LDS - by score, by group, and the
+ * groups by their score -, 28 bytes per entry: 4096 entries are 112 KiB of a CU's 160. The sum of a group is sequential by
+ * contract; m <= 64 keeps it a short loop of one thread.
+ * The call shares the score calls' per-replica stream, mutex and recycled scratch and takes turns with them; it is safe
+ * beside searches, filtered and exact calls. It adds no index array; its scratch is freed by sgpu_index_destroy or a new
+ * upload. A launch takes whole queries only: SGPU_SCORE_CHUNK (candidates per launch, default 2^20) cuts between
+ * queries, a query of more candidates than that goes alone, and a run of queries without any candidate is no launch. */
+sgpu_status sgpu_collapse_documents(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups,
+    uint32_t m, uint32_t k,
+    uint32_t* out_groups, float* out_scores, uint64_t* out_best_ids, float* out_best_scores,
+    uint32_t* out_members, uint32_t* out_n);
+/* The same on the host cores (needs no upload): the arbiter of the contract above, the device call returns its bits;
+ * the same checks without the device ones. num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_collapse_documents_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups,
+    uint32_t m, uint32_t k, uint32_t num_threads,
+    uint32_t* out_groups, float* out_scores, uint64_t* out_best_ids, float* out_best_scores,
+    uint32_t* out_members, uint32_t* out_n);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

@@ -66,6 +66,13 @@ sgpu_status sgpu_debug_expand_stats(sgpu_index* idx, uint32_t replica, double* o
  * its longest query, 0}; SGPU_EINVAL before the replica's first score call. The environment name SGPU_DIVERSIFY_GRID, read
  * per call and honoured under the same switch, lowers the grid (each workgroup then takes many queries in turn) */
 sgpu_status sgpu_debug_diversify_stats(sgpu_index* idx, uint32_t replica, double* out8);
+/* what the last sgpu_collapse_documents call on `replica` measured: out8 = {device ms of its score kernels (HIP events),
+ * launches, 1 = dense weight table / 0 = hash table, grid, workgroup size and LDS bytes of the score kernel's last launch,
+ * device ms of the selection kernels, selection kernel launches (one per tier of list lengths - up to 128, 512, 1024 and
+ * 4096 entries - that a launch has a query in)}; SGPU_EINVAL before the replica's first score call. The environment name
+ * SGPU_COLLAPSE_GRID, read per call and honoured under the same switch, lowers the selection's grid (each workgroup then
+ * takes many queries in turn) */
+sgpu_status sgpu_debug_collapse_stats(sgpu_index* idx, uint32_t replica, double* out8);
 /* the accumulate launches of the last sgpu_exact_search_device[_filtered] call on `replica`: one per chunk of queries whose
  * candidates (n_ranges x k x 8 bytes per query) fit the candidate buffer of 256 MiB; the environment name
  * SGPU_EXACT_CAND_BYTES, read per call and honoured under the same switch, lowers that size. SGPU_EINVAL before the

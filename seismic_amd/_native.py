@@ -99,6 +99,9 @@ def lib():
                                                vp, vp, vp, vp]
         L.sgpu_diversify_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_float, C.c_float, C.c_uint32,
                                                     C.c_uint32, vp, vp, vp, vp]
+        L.sgpu_collapse_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32] + [vp] * 6
+        L.sgpu_collapse_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32] + [vp] * 6
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -595,6 +598,55 @@ class NativeIndex:
         check(fn(self.h, int(replica), _p(out)))
         return dict(kernel_ms=float(out[0]), launches=int(out[1]), grid=int(out[2]), block=int(out[3]), lds=int(out[4]),
                     dense=int(out[5]), rounds=int(out[6]))
+
+    # ---- the k best groups of each query's candidates ----
+    @staticmethod
+    def _collapse_buffers(q_off, comps, vals, cand_off, cand_ids, cand_groups, m, k):
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        cand_groups = np.ascontiguousarray(cand_groups, np.uint32)
+        if len(cand_groups) != len(cand_ids):
+            raise ValueError("%d candidates but %d group keys" % (len(cand_ids), len(cand_groups)))
+        nq, m, k = len(q_off) - 1, int(m), int(k)
+        if not (0 <= k < 2 ** 32 and 0 <= m < 2 ** 32):
+            raise ValueError("m = %d, k = %d" % (m, k))
+        rows = (max(nq, 1), k if 1 <= k <= 1024 else 1)   # (a k the library refuses: nothing is written)
+        out = (np.zeros(rows, np.uint32), np.zeros(rows, np.float32), np.zeros(rows, np.uint64), np.zeros(rows, np.float32),
+               np.zeros(rows, np.uint32), np.zeros(max(nq, 1), np.uint32))
+        if not len(cand_ids):
+            cand_ids, cand_groups = np.zeros(1, np.uint64), np.zeros(1, np.uint32)
+        return q_off, comps, vals, cand_off, cand_ids, cand_groups, nq, m, k, out
+
+    def collapse_documents(self, q_off, comps, vals, cand_off, cand_ids, cand_groups, m, k, replica=0):
+        """sgpu_collapse_documents: per query the k <= 1024 best GROUPS of its candidates (given as for score_documents, at
+        most 4096 per query; cand_groups[i] is the u32 group key of entry i). A group's members are its distinct
+        documents, best first (score descending, id ascending); its score is the f32 sum of its first m <= 64 members in
+        that order (m = 1: its best member's score); groups come by score descending, key ascending. Scored and selected
+        on the device of `replica`. Returns (groups u32 [nq, k], scores f32 [nq, k], best ids u64 [nq, k], best scores
+        f32 [nq, k], members u32 [nq, k], n u32 [nq]); slots past n[q] are zero."""
+        q_off, comps, vals, cand_off, cand, grp, nq, m, k, out = self._collapse_buffers(q_off, comps, vals, cand_off, cand_ids,
+                                                                                        cand_groups, m, k)
+        check(lib().sgpu_collapse_documents(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand),
+                                            _p(grp), m, k, *[_p(a) for a in out]))
+        return tuple(a[:nq] for a in out)
+
+    def collapse_documents_host(self, q_off, comps, vals, cand_off, cand_ids, cand_groups, m, k, num_threads=0):
+        """sgpu_collapse_documents_host: the same rows on the host cores (needs no upload), bit-identical."""
+        q_off, comps, vals, cand_off, cand, grp, nq, m, k, out = self._collapse_buffers(q_off, comps, vals, cand_off, cand_ids,
+                                                                                        cand_groups, m, k)
+        check(lib().sgpu_collapse_documents_host(self.h, _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), _p(grp), m,
+                                                 k, int(num_threads), *[_p(a) for a in out]))
+        return tuple(a[:nq] for a in out)
+
+    def debug_collapse_stats(self, replica=0):
+        """sgpu_debug_collapse_stats (test hook): what the last collapse_documents call on `replica` measured."""
+        out = np.zeros(8, np.float64)
+        fn = lib().sgpu_debug_collapse_stats
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        check(fn(self.h, int(replica), _p(out)))
+        return dict(kernel_ms=float(out[0]), launches=int(out[1]), dense=int(out[2]), grid=int(out[3]), block=int(out[4]),
+                    lds=int(out[5]), select_ms=float(out[6]), select_launches=int(out[7]))
 
 
 def _filter_handle(f):

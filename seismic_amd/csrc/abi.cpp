@@ -82,6 +82,11 @@ sgpu_status diversify_documents_device(sgpu_index* idx, uint32_t replica, const 
                                        const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
                                        float mu, uint32_t k, const DiversifyOut& out);
 bool diversify_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+// collapse_documents.hip
+sgpu_status collapse_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                      const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
+                                      const uint32_t* cand_groups, uint32_t m, uint32_t k, const CollapseOut& out);
+bool collapse_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
 const sgpu_index* filter_index(const sgpu_filter* f);
@@ -938,6 +943,33 @@ sgpu_status sgpu_diversify_documents_host(const sgpu_index* idx, const uint64_t*
   if (!idx) return fail(SGPU_EINVAL, "null argument");
   const DiversifyOut out{out_scores, out_penalties, out_doc_ids, out_n};
   return diversify_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, lambda, mu, k, num_threads, out);
+}
+
+sgpu_status sgpu_collapse_documents(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                    uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups,
+                                    uint32_t m, uint32_t k, uint32_t* out_groups, float* out_scores, uint64_t* out_best_ids,
+                                    float* out_best_scores, uint32_t* out_members, uint32_t* out_n) {
+  const CollapseOut out{out_groups, out_scores, out_best_ids, out_best_scores, out_members, out_n};
+  return collapse_documents_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, cand_groups, m, k, out);
+}
+
+sgpu_status sgpu_collapse_documents_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                         uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups,
+                                         uint32_t m, uint32_t k, uint32_t num_threads, uint32_t* out_groups, float* out_scores,
+                                         uint64_t* out_best_ids, float* out_best_scores, uint32_t* out_members, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  const CollapseOut out{out_groups, out_scores, out_best_ids, out_best_scores, out_members, out_n};
+  return collapse_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_groups, m, k, num_threads, out);
+}
+
+// (not part of the boundary: what the last sgpu_collapse_documents call on `replica` measured - out8 = {device ms of its score
+// kernels, launches, 1 = dense table / 0 = hash table, grid, workgroup size and LDS bytes of the score kernel, device ms of the
+// selection kernels, selection kernel launches}; SGPU_EINVAL before the replica's first score call. tools/collapse_probe.py)
+sgpu_status sgpu_debug_collapse_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");
+  if (!collapse_debug_stats(idx, replica, out8)) return fail(SGPU_EINVAL, "no collapse call has run on replica %u", replica);
+  return SGPU_OK;
 }
 
 // (not part of the boundary: what the last sgpu_diversify_documents call on `replica` measured - out8 = {device ms of its

@@ -149,6 +149,25 @@ sgpu_status diversify_check_args(const HostIndex& h, const uint64_t* q_off, cons
 sgpu_status diversify_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                      const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
                                      uint32_t num_threads, const DiversifyOut& out);
+// the k best groups of each query's candidates (sgpu_collapse_documents_host) and checks 1 - 7 both collapse calls run
+constexpr uint32_t kCollapseMaxK = 1024;
+constexpr uint32_t kCollapseMaxM = 64;        // members a group's score sums (a sequential sum by contract)
+constexpr uint64_t kCollapseMaxCand = 4096;   // listed candidates of one query (the device sorts them in LDS)
+struct CollapseOut {   // the outputs of a collapse call: rows of k and a count per query
+  uint32_t* groups;
+  float* scores;
+  uint64_t* best_ids;
+  float* best_scores;
+  uint32_t* members;
+  uint32_t* n;
+};
+// (*max_cand = the candidates of the longest list)
+sgpu_status collapse_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups, uint32_t m,
+                                uint32_t k, const CollapseOut& out, uint32_t* max_nnz, uint32_t* max_cand);
+sgpu_status collapse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                    const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups, uint32_t m,
+                                    uint32_t k, uint32_t num_threads, const CollapseOut& out);
 // score_documents.hip (the state itself: score_state.hpp)
 void score_state_free(ScoreState* s);
 

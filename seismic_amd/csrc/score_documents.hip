@@ -254,13 +254,55 @@ sgpu_status score_state_init(ScoreState* s, int device) {
 
 }  // namespace
 
+// the form of the table, the workgroup size that goes with its LDS and the workgroups a CU holds: a score call's
+sgpu_status score_pass_begin(const HostIndex& h, uint32_t max_nnz, ScorePass* sp) {
+  sp->form = lookup_form(h, max_nnz);
+  const uint32_t lds = sp->form.table_bytes;
+  sp->block = lds > (40u << 10) ? 1024u : (lds > (20u << 10) ? 512u : 256u);
+  int per_cu = 0;
+  const sgpu_status st = kernel_fit(score_kernel(h.comp_width, h.value_type, sp->form.dense), sp->block, lds, &per_cu);
+  if (st != SGPU_OK) return st;
+  if (per_cu < 1) return fail(SGPU_ELIMIT, "the score kernel does not fit on a CU (%u bytes of LDS)", lds);
+  sp->per_cu = (uint32_t)std::min(per_cu, (int)(2048u / sp->block));
+  return SGPU_OK;
+}
+
+sgpu_status score_pass_launch(ScoreState* s, const HostIndex& h, const DevView& view, const ScorePass& sp, const uint64_t* cand_off,
+                              const uint64_t* cand_ids, uint32_t qa, uint32_t qb, uint32_t* grid) {
+  const uint64_t first = cand_off[qa], n_cand = cand_off[qb] - first;
+  s->h_tiles.clear();
+  for (uint32_t q = qa; q < qb; ++q)
+    for (uint64_t pos = cand_off[q]; pos < cand_off[q + 1]; pos += kScoreTile)
+      s->h_tiles.push_back(make_uint4(q, (uint32_t)(pos - first), (uint32_t)std::min<uint64_t>(kScoreTile, cand_off[q + 1] - pos), 0u));
+  sgpu_status st;
+  if ((st = score_reserve(s, s->tiles, s->h_tiles.size() * sizeof(uint4))) != SGPU_OK || (st = stage_ids(s, cand_ids, first, n_cand)) != SGPU_OK ||
+      (st = score_reserve(s, s->scores, n_cand * 4)) != SGPU_OK)
+    return st;
+  HIP_TRY(hipMemcpyAsync(s->tiles.p, s->h_tiles.data(), s->h_tiles.size() * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
+  ScoreArgs a{};
+  a.fwd = view.fwd;
+  a.doc_ref = view.doc_ref;
+  a.q_off = s->q_off.as<const uint64_t>();
+  a.q_comp = s->q_comp.as<const uint32_t>();
+  a.q_val = s->q_val.as<const float>();
+  a.tiles = s->tiles.as<const uint4>();
+  a.cand = s->cand.as<const uint32_t>();
+  a.out = s->scores.as<float>();
+  a.n_tiles = (uint32_t)s->h_tiles.size();
+  a.dim = (uint32_t)h.dim;
+  a.slot_bits = sp.form.slot_bits;
+  a.val_scale = h.val_scale;
+  *grid = (uint32_t)std::min<uint64_t>(a.n_tiles, (uint64_t)s->n_cu * sp.per_cu);
+  return launch_timed(s, score_kernel(h.comp_width, h.value_type, sp.form.dense), *grid, sp.block, sp.form.table_bytes, a);
+}
+
 void score_state_free(ScoreState* s) {
   if (!s) return;
   if (s->device >= 0) (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (DeviceBuffer* b : {&s->q_off, &s->q_comp, &s->q_val, &s->cand_off, &s->tiles, &s->cand, &s->scores, &s->sel_tasks, &s->slots,
                           &s->carry, &s->row_scores, &s->row_ids, &s->row_n, &s->terms, &s->x_comps, &s->x_vals, &s->x_n, &s->x_w,
-                          &s->x_table, &s->d_pen})
+                          &s->x_table, &s->d_pen, &s->c_groups, &s->c_tasks, &s->c_row_groups, &s->c_row_best, &s->c_row_members})
     b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);

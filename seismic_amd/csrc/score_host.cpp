@@ -1,5 +1,6 @@
 // score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host, sgpu_explain_documents_host,
-// sgpu_expand_queries_host and sgpu_diversify_documents_host, and the argument checks they share with the device calls.
+// sgpu_expand_queries_host, sgpu_diversify_documents_host and sgpu_collapse_documents_host, and the argument checks they
+// share with the device calls.
 //
 // The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
@@ -503,6 +504,130 @@ sgpu_status diversify_documents_host(const HostIndex& h, const uint64_t* q_off, 
       for (uint64_t x = s0; x < s1; ++x) dense[h.comp(x)] = 0.0f;
     }
     out.n[q] = r;
+  }
+  return SGPU_OK;
+}
+
+// Checks 1 - 7 of sgpu_collapse_documents, in the header's order.
+sgpu_status collapse_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups, uint32_t m,
+                                uint32_t k, const CollapseOut& out, uint32_t* max_nnz, uint32_t* max_cand) {
+  if (!cand_groups || !out.groups || !out.best_ids || !out.best_scores || !out.members || !out.n) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out.scores, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  *max_cand = 0;
+  for (uint32_t q = 0; q < nq; ++q) {
+    if (cand_off[q + 1] - cand_off[q] > kCollapseMaxCand)
+      return fail(SGPU_ELIMIT, "query %u has %llu candidates (collapsing documents: limit %llu)", q,
+                  (unsigned long long)(cand_off[q + 1] - cand_off[q]), (unsigned long long)kCollapseMaxCand);
+    *max_cand = std::max(*max_cand, (uint32_t)(cand_off[q + 1] - cand_off[q]));
+  }
+  if (m == 0) return fail(SGPU_EINVAL, "m must be at least 1");
+  if (m > kCollapseMaxM) return fail(SGPU_ELIMIT, "m = %u (collapsing documents: limit %u)", m, kCollapseMaxM);
+  if (k == 0) return fail(SGPU_EINVAL, "k must be at least 1");
+  if (k > kCollapseMaxK) return fail(SGPU_ELIMIT, "k = %u (collapsing documents: limit %u)", k, kCollapseMaxK);
+  return SGPU_OK;
+}
+
+// The host twin of collapse_documents.hip, the arbiter of its rows: per query the distinct (group key, id) pairs of its
+// entries, each scored by score_one; the members of a group ordered by score descending and id ascending, the group's
+// score the f32 sum of its first min(m, members) scores added in that order; the groups ordered by that sum descending
+// and key ascending, cut to k. "Descending" is the order of the scores' integer images (ordered_bits), which is the
+// numeric order wherever scores are finite, since -0.0 never occurs: the device's order.
+sgpu_status collapse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                    const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups, uint32_t m,
+                                    uint32_t k, uint32_t num_threads, const CollapseOut& out) {
+  uint32_t max_nnz = 0, max_cand = 0;
+  const sgpu_status vst = collapse_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, cand_groups, m, k, out, &max_nnz, &max_cand);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0) return SGPU_OK;
+  std::memset(out.groups, 0, (size_t)nq * k * sizeof(uint32_t));
+  std::memset(out.scores, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.best_ids, 0, (size_t)nq * k * sizeof(uint64_t));
+  std::memset(out.best_scores, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.members, 0, (size_t)nq * k * sizeof(uint32_t));
+  std::memset(out.n, 0, (size_t)nq * sizeof(uint32_t));
+  if (cand_off[nq] == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  struct Member {
+    uint32_t group;
+    uint64_t id;
+    float score;
+  };
+  struct Group {
+    uint32_t key;
+    float score;
+    uint64_t best_id;
+    float best_score;
+    uint32_t members;
+  };
+  struct Scratch {
+    std::vector<float> table;
+    std::vector<Member> mem;
+    std::vector<Group> groups;
+  };
+  std::vector<Scratch> scratch;
+  try {
+    scratch.assign((size_t)team, Scratch());
+    for (auto& s : scratch) {
+      s.table.assign(h.dim, 0.0f);
+      s.mem.reserve(max_cand);
+      s.groups.reserve(max_cand);
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+    if (cand_off[q + 1] == cand_off[q]) continue;
+#ifdef _OPENMP
+    Scratch& s = scratch[(size_t)omp_get_thread_num()];
+#else
+    Scratch& s = scratch[0];
+#endif
+    float* dense = s.table.data();
+    std::vector<Member>& mem = s.mem;   // (both reserved for the longest list: nothing below allocates)
+    std::vector<Group>& groups = s.groups;
+    mem.clear();
+    groups.clear();
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) mem.push_back(Member{cand_groups[i], cand_ids[i], 0.0f});
+    // the members: the distinct pairs
+    std::sort(mem.begin(), mem.end(), [](const Member& a, const Member& b) { return a.group != b.group ? a.group < b.group : a.id < b.id; });
+    mem.erase(std::unique(mem.begin(), mem.end(), [](const Member& a, const Member& b) { return a.group == b.group && a.id == b.id; }),
+              mem.end());
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
+    for (Member& x : mem) x.score = score_one(h, x.id, dense);
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+    // group by group, its members best first
+    std::sort(mem.begin(), mem.end(), [](const Member& a, const Member& b) {
+      if (a.group != b.group) return a.group < b.group;
+      const uint32_t ka = ordered_bits(a.score), kb = ordered_bits(b.score);
+      return ka != kb ? ka > kb : a.id < b.id;
+    });
+    for (size_t a = 0; a < mem.size();) {
+      size_t b = a;
+      while (b < mem.size() && mem[b].group == mem[a].group) ++b;
+      float sum = mem[a].score;
+      for (size_t i = a + 1; i < b && i < a + m; ++i) sum = sum + mem[i].score;
+      groups.push_back(Group{mem[a].group, sum, mem[a].id, mem[a].score, (uint32_t)(b - a)});
+      a = b;
+    }
+    const size_t n = std::min<size_t>(k, groups.size());
+    std::partial_sort(groups.begin(), groups.begin() + (ptrdiff_t)n, groups.end(), [](const Group& a, const Group& b) {
+      const uint32_t ka = ordered_bits(a.score), kb = ordered_bits(b.score);
+      return ka != kb ? ka > kb : a.key < b.key;
+    });
+    for (size_t i = 0; i < n; ++i) {
+      const size_t o = (size_t)q * k + i;
+      out.groups[o] = groups[i].key;
+      out.scores[o] = groups[i].score;
+      out.best_ids[o] = groups[i].best_id;
+      out.best_scores[o] = groups[i].best_score;
+      out.members[o] = groups[i].members;
+    }
+    out.n[q] = (uint32_t)n;
   }
   return SGPU_OK;
 }

@@ -321,7 +321,8 @@ class _ScoreMixin:
     _score_rows (document ids -> native ids, an unknown id raises KeyError) and _score_name (native id -> document id);
     explain / batch_explain (sgpu_explain_documents: the terms behind a score) and expand / batch_expand
     (sgpu_expand_queries: Rocchio feedback queries) also _score_token (component -> token); diversify / batch_diversify
-    (sgpu_diversify_documents: MMR selection) need what rerank needs."""
+    (sgpu_diversify_documents: MMR selection) need what rerank needs; collapse / batch_collapse (sgpu_collapse_documents:
+    the k best groups) take group keys beside the ids, or look them up in the mapping set_groups keeps."""
 
     def _score_csr(self, query_components, query_values, doc_ids_per_query):
         off, comps, vals = self._score_queries(query_components, query_values)
@@ -453,6 +454,71 @@ class _ScoreMixin:
     def diversify(self, query_components, query_values, doc_ids, k, lam=0.5, mu=0.5, device=None):
         """The MMR selection among the documents `doc_ids` for one query -> [(score, penalty, doc_id)] (batch_diversify)."""
         return self.batch_diversify([query_components], [query_values], [doc_ids], k, lam, mu, device)[0]
+
+    def set_groups(self, mapping):
+        """The group keys (u32) of the documents, for batch_collapse and batch_search_collapsed without explicit keys: a
+        dict document id -> key (a document id the index does not hold raises ValueError), or an array with one key per
+        document in the index's order. None forgets them. Kept on this object only: not saved with the index, and the
+        library never sees it."""
+        if mapping is None:
+            self._groups = None
+            return
+        known = np.ones(self.len, bool)
+        if isinstance(mapping, dict):
+            keys = np.zeros(self.len, np.int64)
+            known[:] = False
+            try:
+                rows = self._score_rows(list(mapping.keys()))
+            except KeyError as e:
+                raise ValueError("set_groups: unknown document id %s" % (e,))
+            keys[rows] = [int(g) for g in mapping.values()]
+            known[rows] = True
+        else:
+            keys = np.asarray(mapping).astype(np.int64).ravel()
+            if len(keys) != self.len:
+                raise ValueError("%d group keys for %d documents" % (len(keys), self.len))
+        if len(keys) and (keys.min() < 0 or keys.max() >= 2 ** 32):
+            raise ValueError("a group key is a u32")
+        self._groups = (keys.astype(np.uint32), known)
+
+    def batch_collapse(self, query_components, query_values, doc_ids_per_query, groups_per_query, k, m=1, device=None):
+        """Field collapsing -> [[(group, score, best_doc_id, best_score, members)]]: per query the k (1 .. 1024) best
+        groups of its candidates (as for batch_score, at most 4096 per query). groups_per_query[q][i] is the u32 group
+        key of candidate i of query q; None: the keys set_groups holds. A group's members are its distinct documents,
+        best first; its score is the f32 sum of its first m (1 .. 64) members in that order (m = 1: MaxP); groups come
+        by score descending, key ascending. sgpu_collapse_documents on the GPU the index is on (device None) or its
+        host twin (device False)."""
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        if groups_per_query is None:
+            table = getattr(self, "_groups", None)
+            if table is None:
+                raise ValueError("no group keys: pass groups_per_query or call set_groups first")
+            at = cand.astype(np.int64)
+            if not table[1][at].all():
+                raise ValueError("no group key for document %r" % (self._score_name(int(at[~table[1][at]][0])),))
+            grp = table[0][at]
+        else:
+            g = [np.asarray(x).astype(np.int64).ravel() for x in groups_per_query]
+            if [len(x) for x in g] != [len(r) for r in rows]:
+                raise ValueError("groups_per_query does not match doc_ids_per_query")
+            grp = np.concatenate(g) if g else np.zeros(0, np.int64)
+            if len(grp) and (grp.min() < 0 or grp.max() >= 2 ** 32):
+                raise ValueError("a group key is a u32")
+            grp = grp.astype(np.uint32)
+        if self._score_on_device(device):
+            out = self._ix.collapse_documents(off, comps, vals, cand_off, cand, grp, m, k)
+        else:
+            out = self._ix.collapse_documents_host(off, comps, vals, cand_off, cand, grp, m, k)
+        gk, sc, ids, bs, mem = [a.tolist() for a in out[:5]]
+        name = self._score_name
+        return [[(g, s, name(d), b, c) for g, s, d, b, c in zip(gk[q][:n], sc[q][:n], ids[q][:n], bs[q][:n], mem[q][:n])]
+                for q, n in enumerate(out[5].tolist())]
+
+    def collapse(self, query_components, query_values, doc_ids, groups, k, m=1, device=None):
+        """The k best groups among the documents `doc_ids` for one query -> [(group, score, best_doc_id, best_score,
+        members)] (batch_collapse)."""
+        return self.batch_collapse([query_components], [query_values], [doc_ids], None if groups is None else [groups], k, m,
+                                   device)[0]
 
     def _batch_rerank_numpy(self,query_components, query_values, doc_ids_per_query, k, device):
         scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
@@ -735,6 +801,20 @@ class _IndexBase(_ScoreMixin):
         expanded = self.batch_expand(query_components, query_values, docs, None, alpha, beta, fb_terms)
         return self.batch_search(queries_ids, [np.asarray(t, dtype=str) for t, _ in expanded], [v for _, v in expanded], k,
                                  query_cut, heap_factor, n_knn=n_knn, sorted=sorted, filter=filter)
+
+    def batch_search_collapsed(self, queries_ids, query_components, query_values, k, query_cut, heap_factor, depth=100, m=1,
+                               n_knn=0, sorted=True, filter=None):
+        """Search, then collapse -> [[(query_id, group, score, best_doc_id, best_score, members)]]: batch_search for `depth`
+        hits per query, batch_collapse of every query's hits under the keys set_groups holds, cut to k groups.
+        Composition of the two calls, nothing else."""
+        if getattr(self, "_groups", None) is None:
+            raise ValueError("no group keys: call set_groups first")
+        hits = self.batch_search(queries_ids, query_components, query_values, depth, query_cut, heap_factor, n_knn=n_knn,
+                                 sorted=sorted, filter=filter)
+        docs = [[d for _, _, d in row] for row in hits]
+        rows = self.batch_collapse(query_components, query_values, docs, None, k, m)
+        qids = [str(x) for x in np.asarray(queries_ids).ravel()]
+        return [[(qids[q],) + r for r in row] for q, row in enumerate(rows)]
 
     def batch_exact_search(self, queries_ids, query_components, query_values, k, device=None, filter=None):
         """Exact top-k over the index's own documents -> [[(query_id, score, doc_id)]] in input order, the rows of
