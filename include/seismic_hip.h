@@ -634,6 +634,64 @@ sgpu_status sgpu_collapse_documents_host(const sgpu_index* idx,
     uint32_t* out_groups, float* out_scores, uint64_t* out_best_ids, float* out_best_scores,
     uint32_t* out_members, uint32_t* out_n);
 
+/* ---- fuse: hybrid fusion of a query's candidates with another retriever's scores ----
+ * Hybrid retrieval on the device: this index's scores fused with the scores of another retriever (a dense ANN index,
+ * BM25, a cross-encoder pass) over the union of both candidate lists; only nq x k rows come back. The reference has no
+ * counterpart. Queries and candidates are given exactly as for sgpu_score_documents (any order, repeats allowed, possibly
+ * none). cand_ext[i] is the other retriever's score of entry i; NaN of any payload means "not in the other list".
+ * Documents. D_q is the set of distinct ids among q's entries. sparse(d) is the bits sgpu_score_documents returns for
+ * (q, d). ext(d) is, over the entries of d whose cand_ext is not NaN, the one with the largest ordered() image; ordered()
+ * is the monotone integer image of f32 bits of sgpu_explain_documents, -0.0 below +0.0. d is ABSENT if it has no such
+ * entry; P_q is the set of documents of D_q that are present.
+ * Ranks are ordinal; ties are broken by id and never shared. rank_s(d) = 1 + the number of d' in D_q with
+ * ordered(sparse(d')) greater, or equal and a smaller id. rank_e(d) is the same over P_q on ordered(ext); it is 0 for an
+ * absent document.
+ * Fused score. All arithmetic is f32, every operation rounded once and never contracted; (float)rank is exact.
+ *   SGPU_FUSE_RRF     fused = fl( fl(w_sparse / fl(rrf_c + (float)rank_s)) + t_e ),
+ *                     t_e = fl(w_ext / fl(rrf_c + (float)rank_e)) if the document is present, else +0.0.
+ *   SGPU_FUSE_MINMAX  lo_s, hi_s are the sparse scores of D_q with the smallest and the largest ordered() image;
+ *                     n_s = (hi_s == lo_s as floats) ? 1.0f : fl( fl(sparse - lo_s) / fl(hi_s - lo_s) ); n_e the same over
+ *                     P_q on ext; fused = fl( fl(w_sparse * n_s) + (present ? fl(w_ext * n_e) : +0.0) ).
+ *   SGPU_FUSE_SUM     fused = fl( fl(w_sparse * sparse) + (present ? fl(w_ext * ext) : +0.0) ).
+ * A document with an intermediate or a result that is not finite, or that is subnormal, is outside this contract and
+ * need not match the host twin (explain and expand make the same kind of reservation).
+ * Rows. Row q of the nq x k row-major outputs holds D_q ordered by ordered(fused bits) descending, then id ascending, cut
+ * to k: out_doc_ids the id, out_scores fused, out_sparse sparse, out_ext ext (+0.0 where absent), out_rank_sparse rank_s,
+ * out_rank_ext rank_e (0 where absent). out_n[q] = min(k, |D_q|). Slots past it are zero in all six arrays; a query
+ * without candidates gets out_n = 0 and zeroed rows.
+ * Consequences. SUM with w_sparse = 1 and w_ext = 0, any cand_ext: out_doc_ids, out_n and out_sparse are exactly the rows
+ * of sgpu_rerank_documents, and out_scores == out_sparse bit for bit (a sparse score is never -0.0, so adding +-0 keeps
+ * it). RRF with w_sparse = 1, w_ext = 0 and rrf_c = 60: the ids are rerank's and out_rank_sparse[q, j] = j + 1. The rows
+ * depend neither on the order in which the entries are listed nor on how the call is cut into launches.
+ * Checks, in this order: null arguments (SGPU_EINVAL; cand_ids, cand_ext and the seven outputs too, also when there is
+ * nothing to do), everything sgpu_score_documents checks in its order, a cand_ext[i] that is +-inf (SGPU_EINVAL; the
+ * message names the first such candidate and its query), an unknown method (SGPU_EINVAL), w_sparse or w_ext not finite
+ * (SGPU_EINVAL), for RRF only an rrf_c that is not finite or < 0 (SGPU_EINVAL), a query with more than 4096 listed
+ * candidates (SGPU_ELIMIT; the message names the query), k == 0 (SGPU_EINVAL), k > 1024 (SGPU_ELIMIT), index not uploaded
+ * or replica out of range (SGPU_EDEVICE), device memory (SGPU_ENOMEM; the index stays usable). nq == 0 is SGPU_OK.
+ * Limits. One team of threads owns a query and nothing leaves LDS between the score kernel and the row: the entries are
+ * sorted by id, the documents by either score, then by the fused one - four sorts, 32 bytes per entry: 4096 entries are
+ * 128 KiB of a CU's 160.
+ * The call shares the score calls' per-replica stream, mutex and recycled scratch and takes turns with them; it is safe
+ * beside searches, filtered and exact calls. It adds no index array; its scratch is freed by sgpu_index_destroy or a new
+ * upload. A launch takes whole queries only: SGPU_SCORE_CHUNK (candidates per launch, default 2^20) cuts between
+ * queries, a query of more candidates than that goes alone, and a run of queries without any candidate is no launch. */
+enum { SGPU_FUSE_RRF = 0, SGPU_FUSE_MINMAX = 1, SGPU_FUSE_SUM = 2 };
+sgpu_status sgpu_fuse_documents(sgpu_index* idx, uint32_t replica,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext,
+    uint32_t method, float w_sparse, float w_ext, float rrf_c, uint32_t k,
+    float* out_scores, uint64_t* out_doc_ids, float* out_sparse, float* out_ext,
+    uint32_t* out_rank_sparse, uint32_t* out_rank_ext, uint32_t* out_n);
+/* The same on the host cores (needs no upload): the arbiter of the contract above, the device call returns its bits;
+ * the same checks without the device ones. num_threads == 0: all host cores (over the queries). */
+sgpu_status sgpu_fuse_documents_host(const sgpu_index* idx,
+    const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+    const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext,
+    uint32_t method, float w_sparse, float w_ext, float rrf_c, uint32_t k, uint32_t num_threads,
+    float* out_scores, uint64_t* out_doc_ids, float* out_sparse, float* out_ext,
+    uint32_t* out_rank_sparse, uint32_t* out_rank_ext, uint32_t* out_n);
+
 /* Seismic's inner binary dataset format (documents.bin / queries.bin: written by the reference's
  * scripts/convert_json_to_inner_format.py:10-27, read by vectorium's read_seismic_format at
  * src/pylib/mod.rs:987,1127): u32 n_vecs; per vector u32 n, n x u32 components, n x f32 values.

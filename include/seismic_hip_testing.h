@@ -73,6 +73,11 @@ sgpu_status sgpu_debug_diversify_stats(sgpu_index* idx, uint32_t replica, double
  * SGPU_COLLAPSE_GRID, read per call and honoured under the same switch, lowers the selection's grid (each workgroup then
  * takes many queries in turn) */
 sgpu_status sgpu_debug_collapse_stats(sgpu_index* idx, uint32_t replica, double* out8);
+/* what the last sgpu_fuse_documents call on `replica` measured: out8 in the slot order of sgpu_debug_collapse_stats (the
+ * tiers of list lengths are the same); SGPU_EINVAL before the replica's first score call. The environment name
+ * SGPU_FUSE_GRID, read per call and honoured under the same switch, lowers the selection's grid (each workgroup then takes
+ * many queries in turn) */
+sgpu_status sgpu_debug_fuse_stats(sgpu_index* idx, uint32_t replica, double* out8);
 /* the accumulate launches of the last sgpu_exact_search_device[_filtered] call on `replica`: one per chunk of queries whose
  * candidates (n_ranges x k x 8 bytes per query) fit the candidate buffer of 256 MiB; the environment name
  * SGPU_EXACT_CAND_BYTES, read per call and honoured under the same switch, lowers that size. SGPU_EINVAL before the

@@ -102,6 +102,10 @@ def lib():
         L.sgpu_collapse_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32] + [vp] * 6
         L.sgpu_collapse_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
                                                    C.c_uint32] + [vp] * 6
+        L.sgpu_fuse_documents.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_float, C.c_float,
+                                          C.c_float, C.c_uint32] + [vp] * 7
+        L.sgpu_fuse_documents_host.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                               C.c_uint32, C.c_uint32] + [vp] * 7
         L.sgpu_synth_generate.argtypes = [C.POINTER(SynthSpec), vp, vp, vp, C.c_uint64, vp, vp, vp,
                                           C.POINTER(C.c_uint64)]
         L.sgpu_dataset_read.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, vp, vp]
@@ -643,6 +647,62 @@ class NativeIndex:
         """sgpu_debug_collapse_stats (test hook): what the last collapse_documents call on `replica` measured."""
         out = np.zeros(8, np.float64)
         fn = lib().sgpu_debug_collapse_stats
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        check(fn(self.h, int(replica), _p(out)))
+        return dict(kernel_ms=float(out[0]), launches=int(out[1]), dense=int(out[2]), grid=int(out[3]), block=int(out[4]),
+                    lds=int(out[5]), select_ms=float(out[6]), select_launches=int(out[7]))
+
+    # ---- hybrid fusion of each query's candidates with another retriever's scores ----
+    FUSE_METHODS = {"rrf": 0, "minmax": 1, "sum": 2}
+
+    @classmethod
+    def _fuse_buffers(cls, q_off, comps, vals, cand_off, cand_ids, cand_ext, method, k):
+        q_off, comps, vals = _csr(q_off, comps, vals)
+        cand_off = np.ascontiguousarray(cand_off, np.uint64)
+        cand_ids = np.ascontiguousarray(cand_ids, np.uint64)
+        cand_ext = np.ascontiguousarray(cand_ext, np.float32)
+        if len(cand_ext) != len(cand_ids):
+            raise ValueError("%d candidates but %d external scores" % (len(cand_ids), len(cand_ext)))
+        method = cls.FUSE_METHODS.get(method, method)
+        nq, k, method = len(q_off) - 1, int(k), int(method)
+        if not (0 <= k < 2 ** 32 and 0 <= method < 2 ** 32):
+            raise ValueError("method = %d, k = %d" % (method, k))
+        rows = (max(nq, 1), k if 1 <= k <= 1024 else 1)   # (a k the library refuses: nothing is written)
+        out = (np.zeros(rows, np.float32), np.zeros(rows, np.uint64), np.zeros(rows, np.float32), np.zeros(rows, np.float32),
+               np.zeros(rows, np.uint32), np.zeros(rows, np.uint32), np.zeros(max(nq, 1), np.uint32))
+        if not len(cand_ids):
+            cand_ids, cand_ext = np.zeros(1, np.uint64), np.zeros(1, np.float32)
+        return q_off, comps, vals, cand_off, cand_ids, cand_ext, nq, method, k, out
+
+    def fuse_documents(self, q_off, comps, vals, cand_off, cand_ids, cand_ext, method, w_sparse, w_ext, rrf_c, k, replica=0):
+        """sgpu_fuse_documents: per query the k <= 1024 best of its candidates (given as for score_documents, at most 4096
+        per query) under the fusion of this index's score with another retriever's: cand_ext[i] is that retriever's score
+        of entry i, NaN where it does not list the document. method: "rrf" (w_sparse / (rrf_c + rank) + w_ext / (rrf_c +
+        rank), ordinal ranks from 1, ties by id), "minmax" (weighted sum of the scores normalised to [0, 1] over the
+        query's documents) or "sum" (weighted sum of the raw scores), or its SGPU_FUSE_* number; a document the other list
+        lacks gets no external term. All f32, see include/seismic_hip.h. Scored and selected on the device of `replica`.
+        Returns (fused f32, ids u64, sparse scores f32, external scores f32, sparse ranks u32, external ranks u32 - all
+        [nq, k] -, n u32 [nq]); slots past n[q] are zero, and so are the external score and rank of an absent document."""
+        q_off, comps, vals, cand_off, cand, ext, nq, method, k, out = self._fuse_buffers(q_off, comps, vals, cand_off, cand_ids,
+                                                                                         cand_ext, method, k)
+        check(lib().sgpu_fuse_documents(self.h, int(replica), _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), _p(ext),
+                                        method, float(w_sparse), float(w_ext), float(rrf_c), k, *[_p(a) for a in out]))
+        return tuple(a[:nq] for a in out)
+
+    def fuse_documents_host(self, q_off, comps, vals, cand_off, cand_ids, cand_ext, method, w_sparse, w_ext, rrf_c, k,
+                            num_threads=0):
+        """sgpu_fuse_documents_host: the same rows on the host cores (needs no upload), bit-identical."""
+        q_off, comps, vals, cand_off, cand, ext, nq, method, k, out = self._fuse_buffers(q_off, comps, vals, cand_off, cand_ids,
+                                                                                         cand_ext, method, k)
+        check(lib().sgpu_fuse_documents_host(self.h, _p(q_off), _p(comps), _p(vals), nq, _p(cand_off), _p(cand), _p(ext), method,
+                                             float(w_sparse), float(w_ext), float(rrf_c), k, int(num_threads),
+                                             *[_p(a) for a in out]))
+        return tuple(a[:nq] for a in out)
+
+    def debug_fuse_stats(self, replica=0):
+        """sgpu_debug_fuse_stats (test hook): what the last fuse_documents call on `replica` measured."""
+        out = np.zeros(8, np.float64)
+        fn = lib().sgpu_debug_fuse_stats
         fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         check(fn(self.h, int(replica), _p(out)))
         return dict(kernel_ms=float(out[0]), launches=int(out[1]), dense=int(out[2]), grid=int(out[3]), block=int(out[4]),

@@ -87,6 +87,11 @@ sgpu_status collapse_documents_device(sgpu_index* idx, uint32_t replica, const u
                                       const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
                                       const uint32_t* cand_groups, uint32_t m, uint32_t k, const CollapseOut& out);
 bool collapse_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+// fuse_documents.hip
+sgpu_status fuse_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext,
+                                  uint32_t method, float w_sparse, float w_ext, float rrf_c, uint32_t k, const FuseOut& out);
+bool fuse_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
 const sgpu_index* filter_index(const sgpu_filter* f);
@@ -960,6 +965,34 @@ sgpu_status sgpu_collapse_documents_host(const sgpu_index* idx, const uint64_t* 
   if (!idx) return fail(SGPU_EINVAL, "null argument");
   const CollapseOut out{out_groups, out_scores, out_best_ids, out_best_scores, out_members, out_n};
   return collapse_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_groups, m, k, num_threads, out);
+}
+
+sgpu_status sgpu_fuse_documents(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext, uint32_t method,
+                                float w_sparse, float w_ext, float rrf_c, uint32_t k, float* out_scores, uint64_t* out_doc_ids,
+                                float* out_sparse, float* out_ext, uint32_t* out_rank_sparse, uint32_t* out_rank_ext, uint32_t* out_n) {
+  const FuseOut out{out_scores, out_doc_ids, out_sparse, out_ext, out_rank_sparse, out_rank_ext, out_n};
+  return fuse_documents_device(idx, replica, q_off, comps, vals, nq, cand_off, cand_ids, cand_ext, method, w_sparse, w_ext, rrf_c, k, out);
+}
+
+sgpu_status sgpu_fuse_documents_host(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                     uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext,
+                                     uint32_t method, float w_sparse, float w_ext, float rrf_c, uint32_t k, uint32_t num_threads,
+                                     float* out_scores, uint64_t* out_doc_ids, float* out_sparse, float* out_ext,
+                                     uint32_t* out_rank_sparse, uint32_t* out_rank_ext, uint32_t* out_n) {
+  if (!idx) return fail(SGPU_EINVAL, "null argument");
+  const FuseOut out{out_scores, out_doc_ids, out_sparse, out_ext, out_rank_sparse, out_rank_ext, out_n};
+  return fuse_documents_host(idx->host, q_off, comps, vals, nq, cand_off, cand_ids, cand_ext, method, w_sparse, w_ext, rrf_c, k,
+                             num_threads, out);
+}
+
+// (not part of the boundary: what the last sgpu_fuse_documents call on `replica` measured - out8 in the slot order of
+// sgpu_debug_collapse_stats; SGPU_EINVAL before the replica's first score call. tools/fuse_probe.py)
+sgpu_status sgpu_debug_fuse_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out8) return fail(SGPU_EINVAL, "null argument");
+  if (!fuse_debug_stats(idx, replica, out8)) return fail(SGPU_EINVAL, "no fuse call has run on replica %u", replica);
+  return SGPU_OK;
 }
 
 // (not part of the boundary: what the last sgpu_collapse_documents call on `replica` measured - out8 = {device ms of its score

@@ -168,6 +168,27 @@ sgpu_status collapse_check_args(const HostIndex& h, const uint64_t* q_off, const
 sgpu_status collapse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                     const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups, uint32_t m,
                                     uint32_t k, uint32_t num_threads, const CollapseOut& out);
+// hybrid fusion of each query's candidates with another retriever's scores (sgpu_fuse_documents_host) and checks 1 - 9 both
+// fuse calls run
+constexpr uint32_t kFuseMaxK = 1024;
+constexpr uint64_t kFuseMaxCand = 4096;   // listed candidates of one query (the device sorts them in LDS)
+struct FuseOut {   // the outputs of a fuse call: rows of k and a count per query
+  float* scores;
+  uint64_t* doc_ids;
+  float* sparse;
+  float* ext;
+  uint32_t* rank_sparse;
+  uint32_t* rank_ext;
+  uint32_t* n;
+};
+// (*max_cand = the candidates of the longest list)
+sgpu_status fuse_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                            const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext, uint32_t method,
+                            float w_sparse, float w_ext, float rrf_c, uint32_t k, const FuseOut& out, uint32_t* max_nnz,
+                            uint32_t* max_cand);
+sgpu_status fuse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext, uint32_t method,
+                                float w_sparse, float w_ext, float rrf_c, uint32_t k, uint32_t num_threads, const FuseOut& out);
 // score_documents.hip (the state itself: score_state.hpp)
 void score_state_free(ScoreState* s);
 

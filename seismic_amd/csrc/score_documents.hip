@@ -302,7 +302,8 @@ void score_state_free(ScoreState* s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (DeviceBuffer* b : {&s->q_off, &s->q_comp, &s->q_val, &s->cand_off, &s->tiles, &s->cand, &s->scores, &s->sel_tasks, &s->slots,
                           &s->carry, &s->row_scores, &s->row_ids, &s->row_n, &s->terms, &s->x_comps, &s->x_vals, &s->x_n, &s->x_w,
-                          &s->x_table, &s->d_pen, &s->c_groups, &s->c_tasks, &s->c_row_groups, &s->c_row_best, &s->c_row_members})
+                          &s->x_table, &s->d_pen, &s->c_groups, &s->c_tasks, &s->c_row_groups, &s->c_row_best, &s->c_row_members,
+                          &s->f_ext, &s->f_row_sparse, &s->f_row_ext, &s->f_row_rank_s, &s->f_row_rank_e})
     b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);

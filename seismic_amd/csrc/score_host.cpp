@@ -1,6 +1,6 @@
 // score_host.cpp — sgpu_score_documents_host, sgpu_rerank_documents_host, sgpu_explain_documents_host,
-// sgpu_expand_queries_host, sgpu_diversify_documents_host and sgpu_collapse_documents_host, and the argument checks they
-// share with the device calls.
+// sgpu_expand_queries_host, sgpu_diversify_documents_host, sgpu_collapse_documents_host and sgpu_fuse_documents_host, and the
+// argument checks they share with the device calls.
 //
 // The host twin of score_documents.hip: the same score, bit for bit - 16 accumulators, element e of the document to
 // accumulator (e / 8) % 16 in increasing e, the partials combined by t[j] += t[j ^ s], s = 8, 4, 2, 1; f32 multiply then
@@ -626,6 +626,173 @@ sgpu_status collapse_documents_host(const HostIndex& h, const uint64_t* q_off, c
       out.best_ids[o] = groups[i].best_id;
       out.best_scores[o] = groups[i].best_score;
       out.members[o] = groups[i].members;
+    }
+    out.n[q] = (uint32_t)n;
+  }
+  return SGPU_OK;
+}
+
+// Checks 1 - 9 of sgpu_fuse_documents, in the header's order.
+sgpu_status fuse_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                            const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext, uint32_t method,
+                            float w_sparse, float w_ext, float rrf_c, uint32_t k, const FuseOut& out, uint32_t* max_nnz,
+                            uint32_t* max_cand) {
+  if (!cand_ext || !out.doc_ids || !out.sparse || !out.ext || !out.rank_sparse || !out.rank_ext || !out.n) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status vst = score_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, out.scores, max_nnz);
+  if (vst != SGPU_OK) return vst;
+  for (uint32_t q = 0; q < nq; ++q)
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i)
+      if (std::isinf(cand_ext[i]))
+        return fail(SGPU_EINVAL, "query %u: the external score of candidate %llu (document id %llu) is infinite", q,
+                    (unsigned long long)(i - cand_off[q]), (unsigned long long)cand_ids[i]);
+  if (method != SGPU_FUSE_RRF && method != SGPU_FUSE_MINMAX && method != SGPU_FUSE_SUM) return fail(SGPU_EINVAL, "unknown fusion method %u", method);
+  if (!std::isfinite(w_sparse)) return fail(SGPU_EINVAL, "w_sparse is not finite");
+  if (!std::isfinite(w_ext)) return fail(SGPU_EINVAL, "w_ext is not finite");
+  if (method == SGPU_FUSE_RRF && !(std::isfinite(rrf_c) && rrf_c >= 0.0f)) return fail(SGPU_EINVAL, "rrf_c is not a finite number >= 0");
+  *max_cand = 0;
+  for (uint32_t q = 0; q < nq; ++q) {
+    if (cand_off[q + 1] - cand_off[q] > kFuseMaxCand)
+      return fail(SGPU_ELIMIT, "query %u has %llu candidates (fusing documents: limit %llu)", q,
+                  (unsigned long long)(cand_off[q + 1] - cand_off[q]), (unsigned long long)kFuseMaxCand);
+    *max_cand = std::max(*max_cand, (uint32_t)(cand_off[q + 1] - cand_off[q]));
+  }
+  if (k == 0) return fail(SGPU_EINVAL, "k must be at least 1");
+  if (k > kFuseMaxK) return fail(SGPU_ELIMIT, "k = %u (fusing documents: limit %u)", k, kFuseMaxK);
+  return SGPU_OK;
+}
+
+// The host twin of fuse_documents.hip, the arbiter of its rows: per query the distinct ids of its entries, each with the
+// largest external score listed for it that is no NaN (by ordered_bits; none: absent) and scored once by score_one; the
+// ordinal ranks of both orders from two sorts (ordered_bits descending, id ascending); the fused score of the header in
+// plain f32 expressions, one operation per statement (this file is compiled with -ffp-contract=off); the documents
+// ordered by ordered_bits(fused) descending and id ascending, cut to k.
+sgpu_status fuse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext, uint32_t method,
+                                float w_sparse, float w_ext, float rrf_c, uint32_t k, uint32_t num_threads, const FuseOut& out) {
+  uint32_t max_nnz = 0, max_cand = 0;
+  const sgpu_status vst =
+      fuse_check_args(h, q_off, comps, vals, nq, cand_off, cand_ids, cand_ext, method, w_sparse, w_ext, rrf_c, k, out, &max_nnz, &max_cand);
+  if (vst != SGPU_OK) return vst;
+  if (nq == 0) return SGPU_OK;
+  std::memset(out.scores, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.doc_ids, 0, (size_t)nq * k * sizeof(uint64_t));
+  std::memset(out.sparse, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.ext, 0, (size_t)nq * k * sizeof(float));
+  std::memset(out.rank_sparse, 0, (size_t)nq * k * sizeof(uint32_t));
+  std::memset(out.rank_ext, 0, (size_t)nq * k * sizeof(uint32_t));
+  std::memset(out.n, 0, (size_t)nq * sizeof(uint32_t));
+  if (cand_off[nq] == 0) return SGPU_OK;
+  int team = num_threads ? (int)num_threads : host_threads();
+  team = (int)std::max<int64_t>(1, std::min<int64_t>(team, (int64_t)nq));
+  struct Doc {
+    uint64_t id;
+    uint32_t ext_key;   // ordered_bits of the external score, 0: absent (an entry: its own, 0 for NaN)
+    float sparse, ext, fused;
+    uint32_t rank_s, rank_e;
+  };
+  struct Scratch {
+    std::vector<float> table;
+    std::vector<Doc> docs;
+    std::vector<uint32_t> order;
+  };
+  std::vector<Scratch> scratch;
+  try {
+    scratch.assign((size_t)team, Scratch());
+    for (auto& s : scratch) {
+      s.table.assign(h.dim, 0.0f);
+      s.docs.reserve(max_cand);
+      s.order.reserve(max_cand);
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+  const bool f16 = h.value_type == SGPU_VAL_F16;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(team)
+  for (int64_t q = 0; q < (int64_t)nq; ++q) {
+    if (cand_off[q + 1] == cand_off[q]) continue;
+#ifdef _OPENMP
+    Scratch& s = scratch[(size_t)omp_get_thread_num()];
+#else
+    Scratch& s = scratch[0];
+#endif
+    float* dense = s.table.data();
+    std::vector<Doc>& docs = s.docs;   // (both reserved for the longest list: nothing below allocates)
+    std::vector<uint32_t>& order = s.order;
+    docs.clear();
+    for (uint64_t i = cand_off[q]; i < cand_off[q + 1]; ++i)
+      docs.push_back(Doc{cand_ids[i], std::isnan(cand_ext[i]) ? 0u : ordered_bits(cand_ext[i]), 0.0f, 0.0f, 0.0f, 0u, 0u});
+    // the documents: the distinct ids, each with its largest external key
+    std::sort(docs.begin(), docs.end(), [](const Doc& a, const Doc& b) { return a.id != b.id ? a.id < b.id : a.ext_key > b.ext_key; });
+    docs.erase(std::unique(docs.begin(), docs.end(), [](const Doc& a, const Doc& b) { return a.id == b.id; }), docs.end());
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = f16 ? vals[j] : vals[j] * h.val_scale;
+    for (Doc& d : docs) {
+      d.sparse = score_one(h, d.id, dense);
+      d.ext = d.ext_key ? ordered_bits_inv(d.ext_key) : 0.0f;
+    }
+    for (uint64_t j = q_off[q]; j < q_off[q + 1]; ++j) dense[comps[j]] = 0.0f;
+    // the ranks of both orders, and their ends
+    order.clear();
+    for (uint32_t i = 0; i < docs.size(); ++i) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&docs](uint32_t a, uint32_t b) {
+      const uint32_t ka = ordered_bits(docs[a].sparse), kb = ordered_bits(docs[b].sparse);
+      return ka != kb ? ka > kb : docs[a].id < docs[b].id;
+    });
+    for (uint32_t r = 0; r < order.size(); ++r) docs[order[r]].rank_s = r + 1;
+    const float hi_s = docs[order.front()].sparse, lo_s = docs[order.back()].sparse;
+    order.clear();
+    for (uint32_t i = 0; i < docs.size(); ++i)
+      if (docs[i].ext_key) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&docs](uint32_t a, uint32_t b) {
+      return docs[a].ext_key != docs[b].ext_key ? docs[a].ext_key > docs[b].ext_key : docs[a].id < docs[b].id;
+    });
+    for (uint32_t r = 0; r < order.size(); ++r) docs[order[r]].rank_e = r + 1;
+    float hi_e = 0.0f, lo_e = 0.0f;
+    if (!order.empty()) hi_e = docs[order.front()].ext, lo_e = docs[order.back()].ext;
+    // the fused scores: every operation a statement of its own, rounded once
+    const float span_s = hi_s - lo_s, span_e = hi_e - lo_e;
+    for (Doc& d : docs) {
+      const bool present = d.ext_key != 0;
+      float a, b = 0.0f;
+      if (method == SGPU_FUSE_RRF) {
+        const float ds = rrf_c + (float)d.rank_s;
+        a = w_sparse / ds;
+        if (present) {
+          const float de = rrf_c + (float)d.rank_e;
+          b = w_ext / de;
+        }
+      } else if (method == SGPU_FUSE_MINMAX) {
+        float ns = 1.0f, ne = 1.0f;
+        if (!(hi_s == lo_s)) {
+          const float t = d.sparse - lo_s;
+          ns = t / span_s;
+        }
+        a = w_sparse * ns;
+        if (present) {
+          if (!(hi_e == lo_e)) {
+            const float t = d.ext - lo_e;
+            ne = t / span_e;
+          }
+          b = w_ext * ne;
+        }
+      } else {
+        a = w_sparse * d.sparse;
+        if (present) b = w_ext * d.ext;
+      }
+      d.fused = a + b;
+    }
+    const size_t n = std::min<size_t>(k, docs.size());
+    std::partial_sort(docs.begin(), docs.begin() + (ptrdiff_t)n, docs.end(), [](const Doc& a, const Doc& b) {
+      const uint32_t ka = ordered_bits(a.fused), kb = ordered_bits(b.fused);
+      return ka != kb ? ka > kb : a.id < b.id;
+    });
+    for (size_t i = 0; i < n; ++i) {
+      const size_t o = (size_t)q * k + i;
+      out.scores[o] = docs[i].fused;
+      out.doc_ids[o] = docs[i].id;
+      out.sparse[o] = docs[i].sparse;
+      out.ext[o] = docs[i].ext;
+      out.rank_sparse[o] = docs[i].rank_s;
+      out.rank_ext[o] = docs[i].rank_e;
     }
     out.n[q] = (uint32_t)n;
   }

@@ -1,6 +1,6 @@
 // score_state.hpp — what the launchers of the candidate calls share (score_run in score_documents.hip with the selection of
 // rerank_select.hip behind it, expand_run in expand_queries.hip, diversify_run in diversify_documents.hip, collapse_run in
-// collapse_documents.hip): the replica's
+// collapse_documents.hip, fuse_run in fuse_documents.hip): the replica's
 // stream, mutex and recycled scratch, and the steps every launcher takes - the form of the weight table, the candidates
 // a launch may take, the call's queries and a launch's ids staged, the cut of a call into launches of whole queries,
 // the events around a kernel. The kernels' side of the same calls is score_lookup.hpp.
@@ -53,15 +53,19 @@ struct ScoreState {
   // collapse: a launch's group keys and the queries of its selection launches by tier, the call's rows (group keys, best
   // members' scores, member counts; group scores, best ids and counts: rerank's row buffers)
   DeviceBuffer c_groups, c_tasks, c_row_groups, c_row_best, c_row_members;
+  // fuse: a launch's external scores (its queries by tier: collapse's c_tasks), the call's rows (sparse and external scores,
+  // both ranks; fused scores, ids and counts: rerank's row buffers)
+  DeviceBuffer f_ext, f_row_sparse, f_row_ext, f_row_rank_s, f_row_rank_e;
   std::vector<uint4> h_tiles;   // host staging of a launch
   std::vector<uint32_t> h_ids;
   std::vector<std::vector<SelTask>> sel_rounds;   // [round * tiers + tier]
   std::vector<SelTask> h_sel_tasks;
-  std::vector<uint32_t> h_col_tasks;   // collapse: a launch's queries by tier
+  std::vector<uint32_t> h_col_tasks;   // collapse, fuse: a launch's queries by tier
   CallStats score_stats;       // score, rerank, explain; extra: device ms of the selection kernels, merge rounds run
   CallStats expand_stats;      // extra: bytes of the global tables
   CallStats diversify_stats;   // extra: rounds of the call's longest query
   CallStats collapse_stats;    // extra: device ms of the selection kernels, selection launches
+  CallStats fuse_stats;        // the same
 };
 
 // score_documents.hip: the replica's state, made on its first candidate call; and what a sgpu_debug_*_stats hook reports
@@ -166,8 +170,8 @@ inline sgpu_status launch_done(ScoreState* s, CallStats* cs) {
   return SGPU_OK;
 }
 
-// ---- score_documents.hip: the score kernel for a launcher of another file (collapse_documents.hip). score_pass_begin picks
-// the kernel's form and geometry for a call whose queries are staged; score_pass_launch scores the candidates of the whole
+// ---- score_documents.hip: the score kernel for a launcher of another file (collapse_documents.hip, fuse_documents.hip).
+// score_pass_begin picks the kernel's form and geometry for a call whose queries are staged; score_pass_launch scores the candidates of the whole
 // queries [qa, qb) - tiles cut, ids staged, one score per candidate to s->scores in the candidates' order, the kernel
 // between ev0 and ev1 -, and what the caller enqueues behind it reads s->scores and s->cand on the same stream.
 struct ScorePass {

@@ -322,7 +322,8 @@ class _ScoreMixin:
     explain / batch_explain (sgpu_explain_documents: the terms behind a score) and expand / batch_expand
     (sgpu_expand_queries: Rocchio feedback queries) also _score_token (component -> token); diversify / batch_diversify
     (sgpu_diversify_documents: MMR selection) need what rerank needs; collapse / batch_collapse (sgpu_collapse_documents:
-    the k best groups) take group keys beside the ids, or look them up in the mapping set_groups keeps."""
+    the k best groups) take group keys beside the ids, or look them up in the mapping set_groups keeps; fuse / batch_fuse
+    (sgpu_fuse_documents: hybrid fusion) take another retriever's scores beside the ids."""
 
     def _score_csr(self, query_components, query_values, doc_ids_per_query):
         off, comps, vals = self._score_queries(query_components, query_values)
@@ -519,6 +520,37 @@ class _ScoreMixin:
         members)] (batch_collapse)."""
         return self.batch_collapse([query_components], [query_values], [doc_ids], None if groups is None else [groups], k, m,
                                    device)[0]
+
+    def batch_fuse(self, query_components, query_values, doc_ids_per_query, ext_scores_per_query, k, method="rrf", w_sparse=1.0,
+                   w_ext=1.0, rrf_c=60.0, device=None):
+        """Hybrid fusion -> [[(fused, doc_id, sparse, ext, rank_sparse, rank_ext)]], best first: per query the k (1 .. 1024)
+        best of its candidates (as for batch_score, at most 4096 per query) under the fusion of this index's score with
+        another retriever's. ext_scores_per_query[q][i] is that retriever's score of candidate i of query q, NaN (or None)
+        where it does not list the document; of a document given more than once the largest counts. method "rrf": w_sparse /
+        (rrf_c + rank_sparse) + w_ext / (rrf_c + rank_ext), ordinal ranks from 1; "minmax": the weighted sum of both
+        scores normalised to [0, 1] over the query's documents; "sum": the weighted sum of the raw scores. A document the
+        other list lacks gets no external term; its ext and rank_ext come back as 0.0 and 0. sgpu_fuse_documents on the
+        GPU the index is on (device None) or its host twin (device False)."""
+        off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
+        e = [np.array([np.nan if x is None else x for x in row], np.float32).ravel() for row in ext_scores_per_query]
+        if [len(x) for x in e] != [len(r) for r in rows]:
+            raise ValueError("ext_scores_per_query does not match doc_ids_per_query")
+        ext = np.concatenate(e) if e else np.zeros(0, np.float32)
+        if self._score_on_device(device):
+            out = self._ix.fuse_documents(off, comps, vals, cand_off, cand, ext, method, w_sparse, w_ext, rrf_c, k)
+        else:
+            out = self._ix.fuse_documents_host(off, comps, vals, cand_off, cand, ext, method, w_sparse, w_ext, rrf_c, k)
+        fs, ids, sp, ex, rs, re = [a.tolist() for a in out[:6]]
+        name = self._score_name
+        return [[(f, name(d), s, x, a, b) for f, d, s, x, a, b in zip(fs[q][:n], ids[q][:n], sp[q][:n], ex[q][:n], rs[q][:n], re[q][:n])]
+                for q, n in enumerate(out[6].tolist())]
+
+    def fuse(self, query_components, query_values, doc_ids, ext_scores, k, method="rrf", w_sparse=1.0, w_ext=1.0, rrf_c=60.0,
+             device=None):
+        """The k best of the documents `doc_ids` for one query under the fusion with `ext_scores` -> [(fused, doc_id,
+        sparse, ext, rank_sparse, rank_ext)] (batch_fuse)."""
+        return self.batch_fuse([query_components], [query_values], [doc_ids], [ext_scores], k, method, w_sparse, w_ext, rrf_c,
+                               device)[0]
 
     def _batch_rerank_numpy(self,query_components, query_values, doc_ids_per_query, k, device):
         scores, rows = self._batch_score_native(query_components, query_values, doc_ids_per_query, device)
@@ -813,6 +845,27 @@ class _IndexBase(_ScoreMixin):
                                  sorted=sorted, filter=filter)
         docs = [[d for _, _, d in row] for row in hits]
         rows = self.batch_collapse(query_components, query_values, docs, None, k, m)
+        qids = [str(x) for x in np.asarray(queries_ids).ravel()]
+        return [[(qids[q],) + r for r in row] for q, row in enumerate(rows)]
+
+    def batch_search_fused(self, queries_ids, query_components, query_values, external_hits, k, query_cut, heap_factor,
+                           depth=100, method="rrf", w_sparse=1.0, w_ext=1.0, rrf_c=60.0, n_knn=0, sorted=True, filter=None):
+        """Hybrid search -> [[(query_id, fused, doc_id, sparse, ext, rank_sparse, rank_ext)]]: batch_search for `depth` hits
+        per query, their union with external_hits[q] - the other retriever's list of (doc_id, score) -, batch_fuse over
+        it, cut to k. A document the search found and the external list lacks is absent there (ext = NaN); one the
+        external list alone holds is scored by the fusion like any other. Composition of the two calls, nothing else."""
+        hits = self.batch_search(queries_ids, query_components, query_values, depth, query_cut, heap_factor, n_knn=n_knn,
+                                 sorted=sorted, filter=filter)
+        if len(external_hits) != len(hits):
+            raise ValueError("%d queries but %d external lists" % (len(hits), len(external_hits)))
+        docs, ext = [], []
+        for row, other in zip(hits, external_hits):
+            other = [(str(d), float(s)) for d, s in other]
+            listed = {d for d, _ in other}
+            mine = [d for _, _, d in row if d not in listed]
+            docs.append([d for d, _ in other] + mine)
+            ext.append([s for _, s in other] + [np.nan] * len(mine))
+        rows = self.batch_fuse(query_components, query_values, docs, ext, k, method, w_sparse, w_ext, rrf_c)
         qids = [str(x) for x in np.asarray(queries_ids).ravel()]
         return [[(qids[q],) + r for r in row] for q, row in enumerate(rows)]
 
