@@ -12,7 +12,7 @@ import seismic_amd
 from seismic_amd import _native
 from seismic_amd._abi import BuildConfig, IndexDesc
 from seismic_amd.index import _resolve
-from util import random_dataset, random_queries
+from util import random_dataset, random_queries, row_dir_lookup, row_dir_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -576,27 +576,13 @@ def test_hashed_row_directory_finds_every_summary_row_and_nothing_else():
     ix = _native.NativeIndex.build(2, dim, off, comps, vals, BuildConfig.defaults(n_postings=300, centroid_fraction=0.2))
     a = orc.desc_arrays(ix.desc)
     L = _native.lib()
-    L.sgpu_debug_row_dir.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
     nw, bits = ctypes.c_uint64(0), ctypes.c_uint32(0)
-    assert L.sgpu_debug_row_dir(ix.h, None, 0, ctypes.byref(nw), ctypes.byref(bits)) == 0
     n_rows = int(ix.desc.n_rows)
-    nbk = bits.value                   # buckets of four slots, at most 60 % full
-    assert nbk > 0 and nw.value == 16 * nbk and 0 < n_rows <= 0.6 * 4 * nbk + 4
-    tab = np.zeros(nw.value, np.uint32)
-    assert L.sgpu_debug_row_dir(ix.h, tab.ctypes.data_as(ctypes.c_void_p), nw.value, ctypes.byref(nw), ctypes.byref(bits)) == 0
-    tab = tab.reshape(-1, 4, 4)     # [bucket][slot][word]
+    tab, nbk = row_dir_table(ix)       # buckets of four slots, at most 60 % full
+    assert nbk > 0 and tab.shape == (nbk, 4, 4) and 0 < n_rows <= 0.6 * 4 * nbk + 4
 
     def lookup(key):
-        b = (((key * 2654435761) & 0xffffffff) * nbk) >> 32
-        for _ in range(nbk + 1):
-            keys = tab[b, :, 0]
-            hit = np.nonzero(keys == key)[0]
-            if len(hit):
-                return tab[b, hit[0]]
-            if np.any(keys == 0xffffffff):
-                return None
-            b = 0 if b + 1 == nbk else b + 1
-        raise AssertionError("probe sequence does not end")
+        return row_dir_lookup(tab, nbk, key)[0]
 
     lrs, rc, rp = a["list_row_start"], a["row_comp"], a["row_ptr"]
     sb, lbs = a["sum_bid"], a["list_block_start"]

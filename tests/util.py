@@ -84,3 +84,39 @@ def desc_diff(a, b):
 def desc_equal(a, b):
     diff = desc_diff(a, b)
     assert diff is None, diff
+
+
+def row_dir_bucket(key, n_buckets):
+    """device_types.hpp: row_dir_bucket restated - hash, then multiply-high onto [0, n_buckets)."""
+    return (((int(key) * 2654435761) & 0xffffffff) * int(n_buckets)) >> 32
+
+
+def row_dir_table(ix):
+    """The hashed row directory as uploaded (sgpu_debug_row_dir): (table [bucket][slot][word] u32, buckets); buckets == 0
+    where the index has none (u32 components)."""
+    import ctypes
+    L = _native.lib()
+    L.sgpu_debug_row_dir.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
+    nw, nbk = ctypes.c_uint64(0), ctypes.c_uint32(0)
+    assert L.sgpu_debug_row_dir(ix.h, None, 0, ctypes.byref(nw), ctypes.byref(nbk)) == 0
+    if nbk.value == 0:
+        return np.zeros((0, 4, 4), np.uint32), 0
+    assert nw.value == 16 * nbk.value
+    tab = np.zeros(nw.value, np.uint32)
+    assert L.sgpu_debug_row_dir(ix.h, tab.ctypes.data_as(ctypes.c_void_p), nw.value, ctypes.byref(nw), ctypes.byref(nbk)) == 0
+    return tab.reshape(-1, 4, 4), nbk.value
+
+
+def row_dir_lookup(tab, n_buckets, key):
+    """The kernel's walk (search_stage01.inc: build_row_table) restated: (entry words, bucket it was found in) of `key`, or
+    (None, bucket whose empty slot ended the walk)."""
+    b = row_dir_bucket(key, n_buckets)
+    for _ in range(n_buckets + 1):
+        keys = tab[b, :, 0]
+        hit = np.nonzero(keys == key)[0]
+        if len(hit):
+            return tab[b, hit[0]], b
+        if np.any(keys == 0xffffffff):
+            return None, b
+        b = 0 if b + 1 == n_buckets else b + 1
+    raise AssertionError("probe sequence does not end")
