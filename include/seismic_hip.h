@@ -389,6 +389,51 @@ sgpu_status sgpu_exact_search_device_filtered(sgpu_index* idx, uint32_t replica,
                                               float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n,
                                               const sgpu_filter* filter);
 
+/* ---- term filters: a filter from must / must-not / should clauses -------------
+ * The `bool` query of a lexical engine over the index's own vocabulary (an index component is a token; tags, languages
+ * and tenants are often encoded as components too). No reference counterpart. The clauses are evaluated against the
+ * forward index - every stored component of every document - not against the pruned posting lists.
+ * A clause MATCHES document d iff d stores `component` and its stored value, decoded to f32 (binary16 -> f32; u8 code
+ * * val_scale, the product rounded once), is >= min_weight; min_weight = -INFINITY: any stored entry matches.
+ * The set: A = { d < n_docs : every MUST clause matches d, no MUST_NOT clause matches d, and the number of SHOULD
+ * clauses that match d is >= min_should }, intersected with `within`'s set when `within` is not NULL.
+ *  - With no MUST clause and min_should == 0, A is every document except the MUST_NOT matches; documents that store
+ *    no component are in it.
+ *  - n_clauses == 0 gives all documents (of `within`).
+ *  - min_should above the number of SHOULD clauses gives the empty set; it is not an error.
+ *  - One component may appear in several clauses; SHOULD clauses are counted per clause, so two SHOULD clauses on one
+ *    component with different thresholds count on their own.
+ *  - The comparison is the IEEE >= on f32: a stored -0.0 matches min_weight = +0.0.
+ *  - A DotVByte index answers as its fixed-u8 twin does.
+ * The result is an ordinary sgpu_filter of `idx`: sgpu_filter_count is the number of matching documents, every
+ * filtered call takes it, and it stays valid across uploads (it depends on the forward index only).
+ * Checks, in this order: (1) NULL idx or out, or NULL clauses with n_clauses > 0: SGPU_EINVAL; (2) an occur outside
+ * 0..2, a component >= dim or a NaN min_weight: SGPU_EINVAL, the message names the first offending clause;
+ * (3) n_clauses > 1024: SGPU_ELIMIT; (4) a `within` of another index: SGPU_EINVAL; (5, device call only) index not
+ * uploaded or replica out of range: SGPU_EDEVICE; the exact file's own limits: SGPU_ELIMIT, as
+ * sgpu_exact_search_device reports them; device memory: SGPU_ENOMEM, and the index stays usable.
+ * sgpu_filter_create_terms_host needs no upload, scans the host forward arrays with num_threads threads (0 = all) and
+ * DEFINES the bits; sgpu_filter_create_terms returns the same words, computed on the device of `replica` from its
+ * exact file (see sgpu_exact_search_device: the first call on a replica builds the file if no exact call has), and
+ * copies them (n_docs / 8 bytes) to the host. The device call runs on the exact file's stream under its mutex:
+ * term-filter calls and exact calls on one replica take turns; searches run beside them. */
+enum { SGPU_TERM_MUST = 0, SGPU_TERM_MUST_NOT = 1, SGPU_TERM_SHOULD = 2 };
+typedef struct sgpu_term_clause {
+  uint32_t component; /* < dim */
+  uint32_t occur;     /* SGPU_TERM_* */
+  float min_weight;   /* the clause matches d iff d stores the component with a decoded value >= min_weight */
+  uint32_t reserved;  /* 0 */
+} sgpu_term_clause;
+sgpu_status sgpu_filter_create_terms(sgpu_index* idx, uint32_t replica, const sgpu_term_clause* clauses,
+                                     uint32_t n_clauses, uint32_t min_should, const sgpu_filter* within,
+                                     sgpu_filter** out);
+sgpu_status sgpu_filter_create_terms_host(sgpu_index* idx, const sgpu_term_clause* clauses, uint32_t n_clauses,
+                                          uint32_t min_should, const sgpu_filter* within, uint32_t num_threads,
+                                          sgpu_filter** out);
+/* The allowed set of any filter as ceil(n_docs / 32) words (at least one), bit d of word d / 32, bits past n_docs
+ * zero. *n_words (may be NULL) is set to the number of words; cap_words below it is SGPU_EINVAL (nothing written). */
+sgpu_status sgpu_filter_get_bits(const sgpu_filter* filter, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words);
+
 /* ---- scores of caller-given documents ----------------------------------------
  * "What does THIS document score for THIS query?": reranking the candidates of another retriever, fusing candidate
  * lists, explaining a hit, re-checking a stored result. The reference has no by-id entry point; its nearest item is

@@ -81,8 +81,12 @@ sgpu_status sgpu_debug_fuse_stats(sgpu_index* idx, uint32_t replica, double* out
 /* the accumulate launches of the last sgpu_exact_search_device[_filtered] call on `replica`: one per chunk of queries whose
  * candidates (n_ranges x k x 8 bytes per query) fit the candidate buffer of 256 MiB; the environment name
  * SGPU_EXACT_CAND_BYTES, read per call and honoured under the same switch, lowers that size. SGPU_EINVAL before the
- * replica's first exact call */
+ * replica's first exact call (0 launches when only sgpu_filter_create_terms has built the replica's exact file so far) */
 sgpu_status sgpu_debug_exact_launches(sgpu_index* idx, uint32_t replica, uint32_t* out_launches);
+/* {kernel ms of the last sgpu_filter_create_terms call on `replica` (HIP events around its one kernel), wall ms of the
+ * build of the replica's exact file, the file's bytes, its ranges of 32768 documents = workgroups of the kernel}.
+ * SGPU_EINVAL before the replica has an exact file */
+sgpu_status sgpu_debug_term_filter_stats(sgpu_index* idx, uint32_t replica, double* out4);
 /* the posting arrays a search on `replica` walks, read back from the device: the replica's own (filter == NULL) or those of
  * the filter's view there, which is obtained as a search obtains it - built on first use or after a new upload or graph,
  * under the filter's mutex; no second build path. sizes5 = {block starts (n_blocks + 1), postings, kNN ids (0: no graph),

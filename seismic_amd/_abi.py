@@ -73,6 +73,18 @@ class SearchParams(C.Structure):
     ]
 
 
+SGPU_TERM_MUST, SGPU_TERM_MUST_NOT, SGPU_TERM_SHOULD = 0, 1, 2
+
+
+class TermClause(C.Structure):
+    _fields_ = [
+        ("component", C.c_uint32),
+        ("occur", C.c_uint32),
+        ("min_weight", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_float),

@@ -74,6 +74,9 @@ def lib():
         L.sgpu_exact_search.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.sgpu_exact_search_device.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.sgpu_filter_create.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
+        L.sgpu_filter_create_terms.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
+        L.sgpu_filter_create_terms_host.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(vp)]
+        L.sgpu_filter_get_bits.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.sgpu_filter_count.argtypes = [vp]
         L.sgpu_filter_count.restype = C.c_uint64
         L.sgpu_filter_device_bytes.argtypes = [vp]
@@ -280,6 +283,20 @@ class NativeIndex:
         """A document filter (sgpu_filter_create): `ids` are the allowed document ids (repeats allowed), or a boolean
         mask of length n_docs. Pass it as filter= to search, batch_search, exact_search and exact_search_device."""
         return NativeFilter(self, ids)
+
+    def make_term_filter(self, clauses, min_should=0, within=None, replica=0, host=False, num_threads=0):
+        """A term filter (sgpu_filter_create_terms[_host]): the documents that satisfy the must / must-not / should
+        `clauses`, each a (component, occur, min_weight) triple (occur one of _abi.SGPU_TERM_*; min_weight -inf: any
+        stored entry) or a numpy array of them with TERM_CLAUSE_DTYPE. within: a NativeFilter to intersect with.
+        host=False: on the device of `replica`, from its exact file; host=True: the host twin that defines the bits."""
+        cl = term_clauses(clauses)
+        wh = None if within is None else _filter_handle(within)
+        h = C.c_void_p()
+        if host:
+            check(lib().sgpu_filter_create_terms_host(self.h, _p(cl), len(cl), int(min_should), wh, int(num_threads), C.byref(h)))
+        else:
+            check(lib().sgpu_filter_create_terms(self.h, int(replica), _p(cl), len(cl), int(min_should), wh, C.byref(h)))
+        return NativeFilter._adopt(self, h)
 
     def debug_posting_view(self, replica=0, filter=None):
         """sgpu_debug_posting_view (a test hook: needs SGPU_TEST_HOOKS=1): the posting arrays a search on `replica` walks,
@@ -709,6 +726,23 @@ class NativeIndex:
                     lds=int(out[5]), select_ms=float(out[6]), select_launches=int(out[7]))
 
 
+TERM_CLAUSE_DTYPE = np.dtype([("component", np.uint32), ("occur", np.uint32), ("min_weight", np.float32),
+                              ("reserved", np.uint32)])   # sgpu_term_clause
+
+
+def term_clauses(clauses):
+    """(component, occur, min_weight) triples, or an array of TERM_CLAUSE_DTYPE -> a contiguous array of sgpu_term_clause."""
+    if isinstance(clauses, np.ndarray) and clauses.dtype == TERM_CLAUSE_DTYPE:
+        return np.ascontiguousarray(clauses)
+    rows = list(clauses)
+    out = np.zeros(len(rows), TERM_CLAUSE_DTYPE)
+    for i, (c, occur, w) in enumerate(rows):
+        if not 0 <= int(c) <= 0xffffffff or not 0 <= int(occur) <= 0xffffffff:
+            raise ValueError("clause %d: component %r / occur %r out of range" % (i, c, occur))
+        out[i] = (int(c), int(occur), w, 0)
+    return out
+
+
 def _filter_handle(f):
     if not isinstance(f, NativeFilter):
         raise TypeError("filter must be a NativeFilter (NativeIndex.make_filter), got %r" % type(f).__name__)
@@ -742,10 +776,32 @@ class NativeFilter:
         self.h = h
         del self._ids
 
+    @classmethod
+    def _adopt(cls, index, handle):
+        """The NativeFilter that owns an sgpu_filter the library has already made (make_term_filter)."""
+        self = cls.__new__(cls)
+        self.index = index
+        self.h = handle
+        return self
+
     @property
     def count(self):
         """Number of allowed documents."""
         return int(lib().sgpu_filter_count(self.h))
+
+    def bits(self):
+        """The allowed set as u32 words (sgpu_filter_get_bits): bit d of word d // 32, ceil(n_docs / 32) words (at least
+        one), the bits past n_docs zero."""
+        n = C.c_uint64(0)
+        lib().sgpu_filter_get_bits(_filter_handle(self), None, 0, C.byref(n))   # (the size; SGPU_EINVAL by contract)
+        out = np.zeros(int(n.value), np.uint32)
+        check(lib().sgpu_filter_get_bits(self.h, _p(out), len(out), C.byref(n)))
+        return out
+
+    def ids(self):
+        """The allowed document ids, ascending (int64)."""
+        b = np.unpackbits(self.bits().view(np.uint8), bitorder="little")
+        return np.flatnonzero(b).astype(np.int64)
 
     def device_bytes(self):
         return int(lib().sgpu_filter_device_bytes(self.h))

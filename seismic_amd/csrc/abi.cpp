@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "host_index.hpp"
+#include "term_filter.hpp"
 
 struct sgpu_batch;
 
@@ -94,8 +95,7 @@ sgpu_status fuse_documents_device(sgpu_index* idx, uint32_t replica, const uint6
 bool fuse_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 // filter.hip
 sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out);
-const sgpu_index* filter_index(const sgpu_filter* f);
-const uint32_t* filter_host_bits(const sgpu_filter* f);
+sgpu_status filter_get_bits(const sgpu_filter* f, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words);
 uint64_t filter_count(const sgpu_filter* f);
 uint64_t filter_device_bytes(const sgpu_filter* f);
 void filter_destroy(sgpu_filter* f);
@@ -642,6 +642,17 @@ sgpu_status sgpu_search_filtered(sgpu_index* idx, const uint32_t* comps, const f
 sgpu_status sgpu_filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, sgpu_filter** out) {
   return filter_create(idx, doc_ids, n, out);
 }
+sgpu_status sgpu_filter_create_terms(sgpu_index* idx, uint32_t replica, const sgpu_term_clause* clauses, uint32_t n_clauses,
+                                     uint32_t min_should, const sgpu_filter* within, sgpu_filter** out) {
+  return term_filter_device(idx, replica, clauses, n_clauses, min_should, within, out);
+}
+sgpu_status sgpu_filter_create_terms_host(sgpu_index* idx, const sgpu_term_clause* clauses, uint32_t n_clauses, uint32_t min_should,
+                                          const sgpu_filter* within, uint32_t num_threads, sgpu_filter** out) {
+  return term_filter_host(idx, clauses, n_clauses, min_should, within, num_threads, out);
+}
+sgpu_status sgpu_filter_get_bits(const sgpu_filter* filter, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words) {
+  return filter_get_bits(filter, out_words, cap_words, n_words);
+}
 uint64_t sgpu_filter_count(const sgpu_filter* filter) { return filter_count(filter); }
 uint64_t sgpu_filter_device_bytes(const sgpu_filter* filter) { return filter_device_bytes(filter); }
 void sgpu_filter_destroy(sgpu_filter* filter) { filter_destroy(filter); }
@@ -1043,6 +1054,15 @@ sgpu_status sgpu_debug_exact_launches(sgpu_index* idx, uint32_t replica, uint32_
   SGPU_HOOK_OR(SGPU_EINVAL);
   if (!idx || !out_launches) return fail(SGPU_EINVAL, "null argument");
   if (!exact_debug_launches(idx, replica, out_launches)) return fail(SGPU_EINVAL, "no exact call has run on replica %u", replica);
+  return SGPU_OK;
+}
+
+// (not part of the boundary: {kernel ms of the last sgpu_filter_create_terms call on `replica`, wall ms of the build of the
+// exact file there, the file's bytes, its ranges}; SGPU_EINVAL before the replica has an exact file. tools/term_filter_probe.py)
+sgpu_status sgpu_debug_term_filter_stats(sgpu_index* idx, uint32_t replica, double* out4) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !out4) return fail(SGPU_EINVAL, "null argument");
+  if (!term_filter_debug_stats(idx, replica, out4)) return fail(SGPU_EINVAL, "replica %u has no exact file", replica);
   return SGPU_OK;
 }
 

@@ -20,12 +20,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "device_prims.hpp"
+#include "exact_file.hpp"
 #include "filter.hpp"
 #include "hip_util.hpp"
 
@@ -33,7 +35,7 @@ namespace sgpu {
 
 namespace {
 
-constexpr uint32_t kRangeBits = 15, kRange = 1u << kRangeBits;   // documents per range (u16 local ids)
+constexpr uint32_t kRangeBits = kExactRangeBits, kRange = kExactRange;   // documents per range (exact_file.hpp)
 constexpr uint32_t kBS = 1024;        // threads of the accumulate kernel
 constexpr uint32_t kE = 8;            // entries per thread and step
 constexpr uint32_t kGroup = 256;      // query components resolved to segments at a time (LDS)
@@ -359,27 +361,15 @@ __global__ __launch_bounds__(kMergeBS) void exact_merge_kernel(const uint64_t* _
 
 }  // namespace
 
-struct ExactFile {
-  int device = -1;
-  uint32_t n_cu = 0;
-  hipStream_t stream = nullptr;
-  uint64_t n_docs = 0, dim = 0;
-  uint32_t n_ranges = 0, f16 = 1;
-  float val_scale = 0.0f;
-  DeviceBuffer ent, off, rbase;   // the file: u32 entries, u32 offsets [range][dim + 1], u64 base per range
-  uint64_t bytes = 0;
-  std::mutex mu;   // one exact call at a time on this file (its stream and scratch)
-  // per-call scratch, grown as calls need it: the staged queries, the chunk's candidates, the call's result rows
-  DeviceBuffer q_off, q_comp, q_val, cand, out_scores, out_ids, out_n;
-  uint32_t last_launches = 0;   // accumulate launches of the last call (sgpu_debug_exact_launches)
-};
-
 void exact_file_free(ExactFile* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  for (DeviceBuffer* b : {&f->ent, &f->off, &f->rbase, &f->q_off, &f->q_comp, &f->q_val, &f->cand, &f->out_scores, &f->out_ids, &f->out_n})
+  for (DeviceBuffer* b : {&f->ent, &f->off, &f->rbase, &f->q_off, &f->q_comp, &f->q_val, &f->cand, &f->out_scores, &f->out_ids, &f->out_n,
+                          &f->tf_clauses, &f->tf_within, &f->tf_bits, &f->tf_count})
     b->release();
+  if (f->tf_e0) (void)hipEventDestroy(f->tf_e0);
+  if (f->tf_e1) (void)hipEventDestroy(f->tf_e1);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;
 }
@@ -520,6 +510,22 @@ static sgpu_status exact_run(ExactFile* f, const uint64_t* q_off, const uint32_t
   return SGPU_OK;
 }
 
+sgpu_status exact_file_get(sgpu_index* idx, uint32_t replica, ExactFile** out, bool* built) {
+  bool fresh = false;
+  const sgpu_status st = replica_state(
+      idx, idx->exact_mu, idx->exact, replica,
+      [&](ExactFile* nf, int device) {
+        fresh = true;
+        const auto t0 = std::chrono::steady_clock::now();
+        const sgpu_status bst = exact_file_build_on(idx->host, device, nf);
+        nf->build_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return bst;
+      },
+      exact_file_free, out);
+  if (built) *built = fresh && st == SGPU_OK;
+  return st;
+}
+
 sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
                                 const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
                                 uint32_t* out_n, const sgpu_filter* filter) {
@@ -531,10 +537,8 @@ sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_
   }
   if (k == 0) return fail(SGPU_EINVAL, "k == 0");
   if (k > kMaxK) return fail(SGPU_ELIMIT, "k = %u exceeds the limit of %u", k, kMaxK);
-  ExactFile* f = nullptr;   // (the replica's exact file, built on its first exact call)
-  const sgpu_status fst = replica_state(
-      idx, idx->exact_mu, idx->exact, replica, [&](ExactFile* nf, int device) { return exact_file_build_on(idx->host, device, nf); },
-      exact_file_free, &f);
+  ExactFile* f = nullptr;   // (the replica's exact file, built on its first exact or term-filter call)
+  const sgpu_status fst = exact_file_get(idx, replica, &f);
   if (fst != SGPU_OK) return fst;
   const FilterDeviceView* fv = nullptr;
   if (filter) {   // (the filter's view on this replica holds its bitmap there)

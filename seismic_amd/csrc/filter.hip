@@ -24,6 +24,7 @@
 #include "device_prims.hpp"
 #include "filter.hpp"
 #include "hip_util.hpp"
+#include "term_filter.hpp"
 
 namespace sgpu {
 
@@ -199,18 +200,36 @@ sgpu_status filter_create(sgpu_index* idx, const uint32_t* doc_ids, uint64_t n, 
     if (doc_ids[i] >= n_docs)
       return fail(SGPU_EINVAL, "filter: document id %u (position %llu) >= n_docs = %llu", doc_ids[i], (unsigned long long)i,
                   (unsigned long long)n_docs);
-  sgpu_filter* f = new (std::nothrow) sgpu_filter();
-  if (!f) return fail(SGPU_ENOMEM, "out of host memory");
+  std::vector<uint32_t> bits;
   try {
-    f->bits.assign((size_t)std::max<uint64_t>((n_docs + 31) / 32, 1), 0u);
+    bits.assign((size_t)std::max<uint64_t>((n_docs + 31) / 32, 1), 0u);
   } catch (const std::bad_alloc&) {
-    delete f;
     return fail(SGPU_ENOMEM, "out of host memory");
   }
+  for (uint64_t i = 0; i < n; ++i) bits[doc_ids[i] >> 5] |= 1u << (doc_ids[i] & 31u);
+  uint64_t count = 0;
+  for (uint32_t w : bits) count += (uint64_t)__builtin_popcount(w);
+  return filter_from_bits(idx, std::move(bits), count, out);
+}
+
+// The one constructor: a filter of `idx` around a finished bitmap (the id list above, the term filters of term_filter.*).
+sgpu_status filter_from_bits(sgpu_index* idx, std::vector<uint32_t>&& bits, uint64_t count, sgpu_filter** out) {
+  sgpu_filter* f = new (std::nothrow) sgpu_filter();
+  if (!f) return fail(SGPU_ENOMEM, "out of host memory");
   f->idx = idx;
-  for (uint64_t i = 0; i < n; ++i) f->bits[doc_ids[i] >> 5] |= 1u << (doc_ids[i] & 31u);
-  for (uint32_t w : f->bits) f->count += (uint64_t)__builtin_popcount(w);
+  f->bits = std::move(bits);
+  f->count = count;
   *out = f;
+  return SGPU_OK;
+}
+
+sgpu_status filter_get_bits(const sgpu_filter* f, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words) {
+  if (!f) return fail(SGPU_EINVAL, "null argument");
+  const uint64_t n = f->bits.size();
+  if (n_words) *n_words = n;   // (set before the size check: a call with cap_words == 0 asks for the size)
+  if (cap_words < n) return fail(SGPU_EINVAL, "filter bits: %llu words given, %llu needed", (unsigned long long)cap_words, (unsigned long long)n);
+  if (!out_words) return fail(SGPU_EINVAL, "null argument");
+  std::copy(f->bits.begin(), f->bits.end(), out_words);
   return SGPU_OK;
 }
 

@@ -221,6 +221,10 @@ class SeismicFilter:
         """HBM the filter holds on the devices (0 before its first GPU search)."""
         return self._f.device_bytes()
 
+    def bits(self):
+        """The allowed set over the index's internal document rows: u32 words, bit d of word d // 32."""
+        return self._f.bits()
+
     def close(self):
         self._f.close()
 
@@ -237,6 +241,37 @@ def _native_filter(owner, filter):
     if isinstance(filter, (str, bytes)):
         raise TypeError("filter= takes a SeismicFilter or an iterable of document ids, not a single id")
     return owner.make_filter(filter)._f
+
+
+def _term_filter(owner, component_of, must, must_not, should, min_should, min_weight, within, device):
+    """make_term_filter of both class families. component_of(term) -> the component, or None for a term the index does
+    not know. An entry of must / must_not / should is a bare term or a (term, min_weight) pair; min_weight= is the
+    threshold of the bare ones (None: any stored entry). A MUST term the index does not know gives the empty filter; an
+    unknown MUST_NOT or SHOULD term matches nothing and is dropped (min_should still counts against the given list's
+    matches, so it may become unreachable). device None: on the GPU when the index is uploaded, else on the host
+    cores; False: the host; an int or True: the GPU (uploaded first if need be)."""
+    default = -np.inf if min_weight is None else float(min_weight)
+    clauses, empty = [], False
+    for occur, entries in ((0, must), (1, must_not), (2, should)):   # SGPU_TERM_MUST, _MUST_NOT, _SHOULD
+        if isinstance(entries, (str, bytes)):
+            raise TypeError("must / must_not / should take an iterable of terms, not a single term")
+        for e in entries:
+            term, w = (e[0], float(e[1])) if isinstance(e, tuple) else (e, default)
+            c = component_of(term)
+            if c is None:
+                empty = empty or occur == 0
+                continue
+            clauses.append((c, occur, w))
+    if within is not None and not isinstance(within, SeismicFilter):
+        raise TypeError("within= takes a SeismicFilter")
+    if within is not None and within.index is not owner:
+        raise ValueError("the filter was made on another index")
+    if empty:
+        return SeismicFilter(owner, owner._ix.make_filter(np.zeros(0, np.int64)))
+    host = device is False or (device is None and not owner._uploaded)
+    if not host:
+        owner._ensure_device()
+    return SeismicFilter(owner, owner._ix.make_term_filter(clauses, min_should, None if within is None else within._f, host=host))
 
 
 # ---------------------------------------------------------------------------
@@ -764,6 +799,17 @@ class _IndexBase(_ScoreMixin):
             rows.append(i)
         return SeismicFilter(self, self._ix.make_filter(np.asarray(rows, np.int64)))
 
+    def make_term_filter(self, must=(), must_not=(), should=(), min_should=0, min_weight=None, within=None, device=None):
+        """A SeismicFilter of the documents that store every `must` token, none of the `must_not` tokens and at least
+        `min_should` of the `should` tokens (sgpu_filter_create_terms: evaluated against every stored component, not
+        the pruned posting lists). An entry is a token or a (token, min_weight) pair: the token counts only where its
+        stored weight is >= min_weight (min_weight= is the default of the bare tokens; None: any stored weight). A
+        `must` token outside the vocabulary gives the empty filter; a `must_not` or `should` token outside it matches
+        nothing. within: a SeismicFilter to intersect with. device None: the GPU when the index is uploaded, else the
+        host cores; False: the host; an int: the GPU. count is the number of matching documents."""
+        tm = self._tm
+        return _term_filter(self, lambda t: tm.get(str(t)), must, must_not, should, min_should, min_weight, within, device)
+
     # ---- scores of given documents (_ScoreMixin) ----------------------
     def _score_queries(self, query_components, query_values):
         return _resolve_batch(query_components, query_values, self._tm, lambda t: np.asarray(t).astype(str))
@@ -977,6 +1023,14 @@ class _RawBase(_ScoreMixin):
         filter= to search and batch_search."""
         return SeismicFilter(self, self._ix.make_filter(np.asarray(list(doc_ids) if not isinstance(doc_ids, np.ndarray)
                                                                    else doc_ids)))
+
+    def make_term_filter(self, must=(), must_not=(), should=(), min_should=0, min_weight=None, within=None, device=None):
+        """As SeismicIndex.make_term_filter, the terms being integer components; one >= dim is outside the vocabulary."""
+        dim = int(self.dim)
+
+        def component_of(t):
+            return int(t) if 0 <= int(t) < dim else None
+        return _term_filter(self, component_of, must, must_not, should, min_should, min_weight, within, device)
 
     def _score_queries(self, query_components, query_values):
         off = np.zeros(len(query_components) + 1, np.uint64)
