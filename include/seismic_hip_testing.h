@@ -12,7 +12,13 @@ extern "C" {
 
 /* team size a host-parallel phase takes for num_threads == 0 (hardware threads capped by the cgroup CPU quota) */
 uint32_t sgpu_debug_host_threads(void);
-/* how sgpu_batch_search cuts a call of nq queries into launches: bounds[2j], bounds[2j+1] = queries [q0, q1) of launch j */
+/* the smallest chunk and the most chunks sgpu_batch_search cuts a call into, as this process applies them: out2 =
+ * {chunk_min, chunk_max} for a call that shares its replica with other calls (shared != 0) or not, and whose chunks the
+ * device would plan (device_plans != 0) or not - SGPU_CHUNK_MIN / SGPU_CHUNK_MAX as the process read them once, else the
+ * rule (seismic_amd/csrc/call_cut.cpp). Needs no index and no device */
+sgpu_status sgpu_debug_cut_rule(uint32_t shared, uint32_t device_plans, uint32_t* out2);
+/* how sgpu_batch_search cuts a call of nq queries into launches (call_cut.cpp: cut_segment, with equal chunks): bounds[2j],
+ * bounds[2j+1] = queries [q0, q1) of launch j */
 uint32_t sgpu_debug_chunk_bounds(uint32_t nq, uint32_t chunk_min, uint32_t chunk_max, uint32_t lanes_free, uint32_t* bounds);
 /* the same for a call of any size (more than 8 x 16384 queries are served in segments, one after the other): every launch
  * of the call in order, at most cap of them written; first_pm: the first chunk's share in per mille (0: equal chunks) */

@@ -184,6 +184,15 @@ def debug_launch_config(heap_factor=1.0, **fields):
     return dict(zip(LAUNCH_CONFIG_OUT, (int(x) for x in out)))
 
 
+def debug_cut_rule(shared, device_plans):
+    """(chunk_min, chunk_max) as this process cuts an entry-point call (test hook sgpu_debug_cut_rule, no device)."""
+    out = np.zeros(2, np.uint32)
+    fn = lib().sgpu_debug_cut_rule
+    fn.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+    check(fn(int(shared), int(device_plans), _p(out)))
+    return int(out[0]), int(out[1])
+
+
 def params(k, query_cut, heap_factor, first_sorted, n_knn=0):
     return SearchParams(k=int(k), query_cut=int(query_cut), heap_factor=float(heap_factor),
                         n_knn=int(n_knn), first_sorted=1 if first_sorted else 0)

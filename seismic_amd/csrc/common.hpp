@@ -24,7 +24,7 @@ bool test_hooks_on();
 // overrides.
 int default_host_threads(int omp_max_threads);
 
-// The largest launch one chunk of an entry-point call becomes (abi.cpp: a call is cut so that no chunk exceeds it) = the
+// The largest launch one chunk of an entry-point call becomes (call_cut.cpp: a call is cut so that no chunk exceeds it) = the
 // largest launch the device plans (device_types.hpp: kDevicePlanMaxQueries, which launch_plan.hip checks against this).
 constexpr uint32_t kChunkQueriesMax = 16384;
 

@@ -67,7 +67,7 @@ Lane* lane_try_acquire(DeviceIndex* d) {
 }
 
 // Is this replica serving several calls at a time? call_enter() = true when another entry-point call is in flight on it
-// now or was within the last 50 ms (abi.cpp then cuts a large call into fewer chunks: the other calls' kernels already
+// now or was within the last 50 ms (cut_rule, call_cut.cpp, then cuts a large call into fewer chunks: the other calls' kernels already
 // hide this call's host side). The short memory matters: request threads that run in lockstep enter at the same instant,
 // and the first of them would see an idle replica every time.
 static inline int64_t mono_us() {

@@ -9,10 +9,10 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device_calls.hpp"   // what these files export to the host side
 #include "device_types.hpp"
 #include "host_index.hpp"
 
-struct sgpu_batch;
 namespace sgpu {
 
 // One stream's worth of launch state. The device-resident batch API (sgpu_batch_*) runs on the
@@ -158,16 +158,12 @@ struct sgpu_batch {
 };
 namespace sgpu {
 
-// device_index.hip
-sgpu_status device_index_set_knn(DeviceIndex* d, const std::vector<uint32_t>& knn, uint32_t knn_dim);
-// launch_plan.hip (device_plan_dots takes d->mu itself; the others touch nothing the lanes share)
+// launch_plan.hip (these touch nothing the lanes share)
 sgpu_status make_plan(const DeviceIndex* d, const uint64_t* h_off, const uint32_t* h_comp, const float* h_val, uint32_t nq,
                       uint32_t query_cut, sgpu_batch_plan* out);
 sgpu_status plan_for(DeviceIndex* d, sgpu_batch* b, uint32_t query_cut, const sgpu_batch_plan** out);
-uint32_t device_plan_dots(DeviceIndex* d, const sgpu_search_params& sp, uint32_t nq, uint32_t cut);
 bool later_chunks_on_host();
 // batch.hip
-void batch_free(sgpu_batch* b);
 // Chooses block size, LDS layout and grid for one search pass and readies the lane for it (caller holds d->mu).
 // (ov: the view to search instead of the replica's own - a filter's, filter.hip; null: the replica's)
 sgpu_status configure(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sgpu_search_params& sp, uint32_t mode, LaunchArgs* a,

@@ -9,8 +9,8 @@
 
 namespace sgpu {
 
-struct DeviceIndex;  // search.hip
-struct ExactFile;    // exact_device.hip
+struct DeviceIndex;  // device_index.hpp
+struct ExactFile;    // exact_file.hpp
 struct ScoreState;   // score_state.hpp
 
 struct HostIndex {
@@ -94,12 +94,19 @@ sgpu_status exact_search_host(const HostIndex& ix, const uint64_t* q_off, const 
                               float* out_scores, uint64_t* out_ids, uint32_t* out_n, const uint32_t* allow = nullptr);
 // exact_device.hip
 void exact_file_free(ExactFile* f);
+sgpu_status exact_search_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                const float* vals, uint32_t nq, uint32_t k, float* out_scores, uint64_t* out_ids,
+                                uint32_t* out_n, const sgpu_filter* filter);
+bool exact_debug_launches(sgpu_index* idx, uint32_t replica, uint32_t* out);
 // score_host.cpp: scores of caller-given documents (sgpu_score_documents_host) and the argument checks both calls run
 constexpr uint32_t kScoreMaxQueryNnz = 8192;   // components of a query (the device's hash table: 2^14 slots, half full)
 sgpu_status score_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                              const uint64_t* cand_off, const uint64_t* cand_ids, const float* out_scores, uint32_t* max_nnz);
 sgpu_status score_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                  const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t num_threads, float* out_scores);
+sgpu_status score_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                   const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
+                                   float* out_scores);
 // the k best distinct candidates of each query (sgpu_rerank_documents_host) and checks 1 - 4 both rerank calls run
 constexpr uint32_t kRerankMaxK = 1024;
 sgpu_status rerank_check_args(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
@@ -108,6 +115,9 @@ sgpu_status rerank_check_args(const HostIndex& h, const uint64_t* q_off, const u
 sgpu_status rerank_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                   const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k, uint32_t num_threads,
                                   float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
+sgpu_status rerank_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                    const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t k,
+                                    float* out_scores, uint64_t* out_doc_ids, uint32_t* out_n);
 // the m best terms behind each candidate's score (sgpu_explain_documents_host) and the checks both explain calls run
 constexpr uint32_t kExplainMaxTerms = 32;
 struct ExplainOut {   // the outputs of an explain call: one score and count per candidate, rows of m per term array
@@ -124,6 +134,9 @@ sgpu_status explain_check_args(const HostIndex& h, const uint64_t* q_off, const 
 sgpu_status explain_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                    const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m, uint32_t num_threads,
                                    const ExplainOut& out);
+sgpu_status explain_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                     const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, uint32_t m,
+                                     const ExplainOut& out);
 // Rocchio feedback queries (sgpu_expand_queries_host) and checks 1 - 6 both expand calls run
 constexpr uint32_t kExpandMaxTerms = 1024;
 constexpr uint64_t kExpandMaxCand = 65536;   // feedback documents of one query
@@ -133,6 +146,9 @@ sgpu_status expand_check_args(const HostIndex& h, const uint64_t* q_off, const u
 sgpu_status expand_queries_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                 const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha, uint32_t t,
                                 uint32_t num_threads, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
+sgpu_status expand_queries_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_w, float alpha,
+                                  uint32_t t, uint32_t* out_comps, float* out_vals, uint32_t* out_n);
 // MMR selection of candidates (sgpu_diversify_documents_host) and checks 1 - 7 both diversify calls run
 constexpr uint32_t kDiversifyMaxK = 256;
 constexpr uint64_t kDiversifyMaxCand = 2048;   // listed candidates of one query (the device keeps their state in LDS)
@@ -149,6 +165,9 @@ sgpu_status diversify_check_args(const HostIndex& h, const uint64_t* q_off, cons
 sgpu_status diversify_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                      const uint64_t* cand_off, const uint64_t* cand_ids, float lambda, float mu, uint32_t k,
                                      uint32_t num_threads, const DiversifyOut& out);
+sgpu_status diversify_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                       const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, float lambda,
+                                       float mu, uint32_t k, const DiversifyOut& out);
 // the k best groups of each query's candidates (sgpu_collapse_documents_host) and checks 1 - 7 both collapse calls run
 constexpr uint32_t kCollapseMaxK = 1024;
 constexpr uint32_t kCollapseMaxM = 64;        // members a group's score sums (a sequential sum by contract)
@@ -168,6 +187,9 @@ sgpu_status collapse_check_args(const HostIndex& h, const uint64_t* q_off, const
 sgpu_status collapse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                     const uint64_t* cand_off, const uint64_t* cand_ids, const uint32_t* cand_groups, uint32_t m,
                                     uint32_t k, uint32_t num_threads, const CollapseOut& out);
+sgpu_status collapse_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps,
+                                      const float* vals, uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids,
+                                      const uint32_t* cand_groups, uint32_t m, uint32_t k, const CollapseOut& out);
 // hybrid fusion of each query's candidates with another retriever's scores (sgpu_fuse_documents_host) and checks 1 - 9 both
 // fuse calls run
 constexpr uint32_t kFuseMaxK = 1024;
@@ -189,8 +211,18 @@ sgpu_status fuse_check_args(const HostIndex& h, const uint64_t* q_off, const uin
 sgpu_status fuse_documents_host(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                 const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext, uint32_t method,
                                 float w_sparse, float w_ext, float rrf_c, uint32_t k, uint32_t num_threads, const FuseOut& out);
+sgpu_status fuse_documents_device(sgpu_index* idx, uint32_t replica, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, const uint64_t* cand_off, const uint64_t* cand_ids, const float* cand_ext,
+                                  uint32_t method, float w_sparse, float w_ext, float rrf_c, uint32_t k, const FuseOut& out);
 // score_documents.hip (the state itself: score_state.hpp)
 void score_state_free(ScoreState* s);
+// what the last candidate call of a kind on `replica` measured (the sgpu_debug_*_stats test hooks; false: none has run) -
+// each in the .hip file of its call, score_debug_stats (score, rerank, explain) in score_documents.hip
+bool score_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+bool expand_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+bool diversify_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+bool collapse_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
+bool fuse_debug_stats(sgpu_index* idx, uint32_t replica, double* out8);
 
 // filter.hip: which filter a launch searches with (f null: none) and on which replica of the index
 struct FilterRef {

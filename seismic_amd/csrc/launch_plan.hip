@@ -139,11 +139,11 @@ sgpu_status debug_plan(const HostIndex& h, const uint64_t* q_off, const uint32_t
 }
 
 // May a launch of nq queries at this query_cut (`cut`: as staged_launch clamps it) be planned on the device? THE predicate:
-// staged_launch decides with it, and abi.cpp's chunk rule asks it with the size of the chunks it is about to cut. Returns
+// staged_launch decides with it, and search_segment (abi.cpp) asks it with the size of the chunks it is about to cut. Returns
 // the block dots the LDS layout of such a launch is sized for - what earlier chunks needed (plan_dots_seen) - or 0: the host
 // plans (sizes out of range, a sorted first list, the hashed lookup of u32 indexes, SGPU_DEVICE_PLAN=0, SGPU_NO_LPT, or no
 // chunk has seeded the cache yet). The knobs are read through the per-call cache, which is refreshed here.
-static_assert((uint32_t)kDevicePlanMaxQueries == kChunkQueriesMax, "abi.cpp cuts calls by kChunkQueriesMax");
+static_assert((uint32_t)kDevicePlanMaxQueries == kChunkQueriesMax, "call_cut.cpp cuts calls by kChunkQueriesMax");
 uint32_t device_plan_dots(DeviceIndex* d, const sgpu_search_params& sp, uint32_t nq, uint32_t cut) {
   env_refresh();
   const bool hash_family = d->comp_width == 4 && d->value_type == SGPU_VAL_F16 && d->view.dim < (1u << 24);

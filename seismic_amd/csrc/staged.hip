@@ -109,7 +109,7 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
     b->device = d->device;
     b->owner = d;
     // twice the need: a lane that has served one chunk of a call cut in four also holds a chunk of a call cut in two (the
-    // number of chunks follows the load of the replica, abi.cpp) - no pinned reallocation in the middle of a stream of calls
+    // number of chunks follows the load of the replica: cut_rule, call_cut.cpp) - no pinned reallocation in the middle of a stream of calls
     // (2.5 x: chunks of one call differ by a few per cent in components; the slack is bounded - the arena exists twice, in
     // HBM and as pinned host memory, per lane: ADVICE r05)
     b->arena_cap = std::max<size_t>(std::min<size_t>(A.total * 5 / 2, A.total + ((size_t)64 << 20)), 1 << 16);
@@ -144,7 +144,7 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
   // one-thread call); on the host for small chunks (microseconds), for the first chunk, for a sorted first list (its
   // sort buffer must hold the chunk's largest first list: the host plan knows it exactly), for query_cut > 16 and for the
   // hashed lookup of u32 indexes (per-query seeds). SGPU_DEVICE_PLAN=0: always the host.
-  // WHO PLANS WHICH CHUNK of a call that abi.cpp cut in several: chunk 0 goes out unplanned (below) with nothing ahead of
+  // WHO PLANS WHICH CHUNK of a call that search_segment (abi.cpp, by the rules of call_cut.cpp) cut in several: chunk 0 goes out unplanned (below) with nothing ahead of
   // its search. A LATER chunk is planned here, on the calling thread, which would otherwise sit in its wait: the previous
   // chunk's persistent workgroups hold every CU until its queries run out, so plan kernels on this chunk's stream cannot
   // start before that tail (they completed 2.7 ms into a 10 000-query call) and the search behind them starts later still.

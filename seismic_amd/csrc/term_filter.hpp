@@ -13,6 +13,10 @@ constexpr uint32_t kTermMaxClauses = 1024;
 // filter.hip
 const sgpu_index* filter_index(const sgpu_filter* f);
 const uint32_t* filter_host_bits(const sgpu_filter* f);
+// (the check of every entry point that takes an index and a filter, which may be null)
+inline sgpu_status foreign_filter(const sgpu_index* idx, const sgpu_filter* filter) {
+  return filter && filter_index(filter) != idx ? fail(SGPU_EINVAL, "the filter was created on another index") : SGPU_OK;
+}
 // A filter of `idx` from a finished bitmap: ceil(n_docs / 32) words (at least one), the bits past n_docs zero; count = its
 // popcount. `bits` is moved from.
 sgpu_status filter_from_bits(sgpu_index* idx, std::vector<uint32_t>&& bits, uint64_t count, sgpu_filter** out);

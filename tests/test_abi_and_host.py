@@ -425,7 +425,7 @@ def test_default_host_thread_count_override_keeps_the_index(monkeypatch):
 
 
 def test_chunk_plan_of_a_call_covers_every_query_once():
-    """How sgpu_batch_search cuts a call into launches (abi.cpp chunk_jobs / chunk_bounds, through the debug export):
+    """How sgpu_batch_search cuts a call into launches (call_cut.cpp cut_segment, through the debug export):
     whatever the sizes, the launches are contiguous, in order, non-empty and cover [0, nq) exactly once."""
     L = ctypes.CDLL(_native.LIB_PATH)
     L.sgpu_debug_chunk_bounds.restype = ctypes.c_uint32

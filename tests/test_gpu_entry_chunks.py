@@ -149,8 +149,50 @@ def child(work, cut_name):
     np.savez(os.path.join(work, "rows_%s.npz" % cut_name), **out)
 
 
+# the child of the rule: SGPU_CHUNK_MIN / SGPU_CHUNK_MAX unset, so the library cuts by its own rule (call_cut.cpp: cut_rule).
+# The sizes at which the 600 and the 1300 rule flip between one launch and two.
+RULE_SIZES = (1199, 1200, 2599, 2600)
+
+
+def rule_child(work):
+    """Per size, on a replica uploaded afresh (its lanes have served nothing): the first call - nothing has told the device
+    what the index needs, the host plans - and a second one, each from this one thread with nothing else on the replica.
+    Recorded per call: what every pool lane reports (sgpu_debug_lane_chunk) and, for device_plans 0 and 1, what
+    sgpu_debug_cut_rule(shared=0, device_plans) and cut_segment under it (sgpu_debug_chunk_bounds) say."""
+    from seismic_amd import _native
+    from util import random_queries
+    ix = _native.NativeIndex.load(os.path.join(work, "index.idx"))
+    L = _native.lib()
+    L.sgpu_debug_lane_chunk.restype = ctypes.c_uint32
+    L.sgpu_debug_lane_chunk.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+    L.sgpu_debug_chunk_bounds.restype = ctypes.c_uint32
+    L.sgpu_debug_chunk_bounds.argtypes = [ctypes.c_uint32] * 4 + [ctypes.c_void_p]
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    out = {}
+    for nq in RULE_SIZES:
+        q = random_queries(200 + nq, nq, DIM, 3, 30)
+        for dp in (0, 1):
+            chunk_min, chunk_max = _native.debug_cut_rule(0, dp)
+            bounds = np.zeros(16, np.uint32)
+            n = L.sgpu_debug_chunk_bounds(nq, chunk_min, chunk_max, 8, p(bounds))
+            out["want.%d.%d" % (nq, dp)] = np.concatenate([[chunk_min, chunk_max], bounds[:2 * n]]).astype(np.int64)
+        ix.upload(0)
+        for call in (0, 1):
+            ix.batch_search(*q, 10, 4, HF, False)
+            lanes = []
+            for lane in range(8):
+                info = np.zeros(4, np.uint32)
+                if L.sgpu_debug_lane_chunk(ix.h, lane, p(info), None, 0):
+                    lanes.append([lane] + [int(x) for x in info])
+            out["lanes.%d.%d" % (nq, call)] = np.array(lanes, np.int64).reshape(-1, 5)
+    np.savez(os.path.join(work, "rows_rule.npz"), **out)
+
+
 if __name__ == "__main__":
-    child(sys.argv[1], sys.argv[2])
+    if sys.argv[2] == "rule":
+        rule_child(sys.argv[1])
+    else:
+        child(sys.argv[1], sys.argv[2])
     sys.exit(0)
 
 import pytest  # noqa: E402
@@ -185,7 +227,7 @@ def runs(tmp_path_factory):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), work, cut_name], env=env, capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, (cut_name, r.stdout[-2000:], r.stderr[-4000:])
         rows[cut_name] = dict(np.load(os.path.join(work, "rows_%s.npz" % cut_name)))
-    return {"ix": ix, "qs": qs, "rows": rows, "oracle": {}}
+    return {"ix": ix, "qs": qs, "rows": rows, "oracle": {}, "work": work}
 
 
 class _FilteredDesc:
@@ -309,3 +351,37 @@ def test_an_invalid_component_in_a_later_chunk_fails_the_call_and_not_the_next(r
 @pytest.mark.parametrize("cut_name", list(CUTS))
 def test_three_request_threads_share_the_lanes(runs, cut_name):
     assert bool(runs["rows"][cut_name]["threads"][0])
+
+
+def test_the_library_cuts_by_the_rule_the_hooks_describe(runs):
+    """SGPU_CHUNK_MIN / SGPU_CHUNK_MAX unset, one request thread on an idle replica (shared = 0), 1199 / 1200 / 2599 / 2600
+    queries - where the 600 and the 1300 rule flip between one launch and two: the pool lanes that served a call, and their
+    [q0, q1), are cut_segment's under sgpu_debug_cut_rule(0, device_plans). device_plans is read off the lanes, not guessed:
+    0 where every chunk of the call was planned by the host (the first call on a fresh replica: nothing has told the device
+    what the index needs), 1 where a chunk went out planned by the device or unplanned. info4 says who planned a chunk, not
+    which rule cut the call; a lone caller takes the pool's lanes in order, so lane 0 always holds this call's first chunk,
+    and a cut into another number of chunks than the rule's shows in that chunk's size. On the fresh replica the lanes that
+    report anything at all are exactly the call's."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SGPU_CHUNK_") and k != "SGPU_DEVICE_PLAN"}
+    env["SGPU_TEST_HOOKS"] = "1"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), runs["work"], "rule"], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    rows = dict(np.load(os.path.join(runs["work"], "rows_rule.npz")))
+    for nq in RULE_SIZES:
+        # the rule itself, as tests/test_entry_chunks_cpu.py pins it, and the launches it leads to at these sizes
+        assert list(rows["want.%d.0" % nq][:2]) == [600, 4] and list(rows["want.%d.1" % nq][:2]) == [1300, 2]
+        assert len(rows["want.%d.0" % nq]) // 2 - 1 == {1199: 1, 1200: 2, 2599: 4, 2600: 4}[nq]   # (at least 600 each, up to four)
+        assert len(rows["want.%d.1" % nq]) // 2 - 1 == {1199: 1, 1200: 1, 2599: 1, 2600: 2}[nq]   # (at least 1300 each, up to two)
+        for call in (0, 1):
+            lanes = rows["lanes.%d.%d" % (nq, call)]
+            print("nq %d call %d: lanes (lane, queries, first query, planner, query_cut) %s" % (nq, call, lanes.tolist()))
+            assert len(lanes) and lanes[0][0] == 0
+            dp = int(lanes[0][3] != 0)   # (who planned the call's first chunk: the host plans it only where the device cannot)
+            if call == 0:
+                assert dp == 0, (nq, lanes.tolist())
+            want = rows["want.%d.%d" % (nq, dp)][2:].reshape(-1, 2)
+            got = [(int(q0), int(q0 + n_)) for _, n_, q0, _, _ in lanes[:len(want)]]
+            assert got == [tuple(int(x) for x in w) for w in want], (nq, call, dp, lanes.tolist(), want.tolist())
+            assert [int(x) for x in lanes[:len(want), 0]] == list(range(len(want)))
+            if call == 0:
+                assert len(lanes) == len(want), (nq, lanes.tolist())   # (no other lane has served anything)
