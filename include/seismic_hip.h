@@ -219,7 +219,7 @@ sgpu_status sgpu_index_build_knn(sgpu_index* idx, uint32_t nknn);
 sgpu_status sgpu_index_set_knn(sgpu_index* idx, const uint32_t* neighbours, uint64_t n_total, uint32_t knn_dim);
 sgpu_status sgpu_index_get_knn(const sgpu_index* idx, const uint32_t** neighbours, uint64_t* n_total,
                                uint32_t* knn_dim);
-/* Bytes resident in HBM after upload (0 before). */
+/* Bytes resident in HBM after upload (0 before), plus the device copies of document columns on all replicas. */
 uint64_t sgpu_index_device_bytes(const sgpu_index* idx);
 /* A DotVByte index (SGPU_VAL_DOTVBYTE; reference src/pylib/dotvbyte.rs:15-22) keeps a document whose component gaps do
  * not fit the packed stream's fields in the raw form (2 bytes per component instead of 1.5): how many documents and
@@ -433,6 +433,89 @@ sgpu_status sgpu_filter_create_terms_host(sgpu_index* idx, const sgpu_term_claus
 /* The allowed set of any filter as ceil(n_docs / 32) words (at least one), bit d of word d / 32, bits past n_docs
  * zero. *n_words (may be NULL) is set to the number of words; cap_words below it is SGPU_EINVAL (nothing written). */
 sgpu_status sgpu_filter_get_bits(const sgpu_filter* filter, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words);
+
+/* ---- document columns: range and set filters, facet counts --------------------
+ * Up to SGPU_MAX_COLUMNS per-document attributes of 32 bits each (a tenant, a category, a timestamp, a price), held with
+ * the index on the host and, once a device call needs them, on the device. No reference counterpart.
+ * sgpu_index_set_column: `values` holds one 32-bit value per document, in the index's document order; n must equal
+ * n_docs (SGPU_EINVAL otherwise). values == NULL with n == 0 drops the column. slot >= SGPU_MAX_COLUMNS or an unknown
+ * type is SGPU_EINVAL. The library copies the values; setting a slot again replaces the column, and its type may
+ * change. For a U32 column the largest value is recorded while it is copied (sgpu_facet_counts checks it). Needs no
+ * upload. Filters made earlier are bitmaps and stay valid.
+ * sgpu_index_get_column: a view of the host copy, valid until the next sgpu_index_set_column of that slot or
+ * sgpu_index_destroy; an empty slot gives *n = 0 and *values = NULL and is not an error (*type is then 0).
+ * A replica's copy of a column is made by the first device call that needs it there, and made again after
+ * sgpu_index_set_column replaced the column or sgpu_index_upload[_many] replaced the replica; dropping a column frees
+ * its copies. sgpu_index_device_bytes counts the copies of all replicas.
+ * Columns are NOT part of the index file: sgpu_index_save does not write them, sgpu_index_load returns an index
+ * without columns, and sgpu_index_convert does not carry them over. The file format is unchanged.
+ * sgpu_index_set_column waits for the column calls running on every replica (it takes their mutex) before it frees or
+ * replaces anything; like sgpu_index_set_knn it must not run beside a HOST call that reads the same column. */
+enum { SGPU_COL_U32 = 0, SGPU_COL_I32 = 1, SGPU_COL_F32 = 2 };
+#define SGPU_MAX_COLUMNS 16
+sgpu_status sgpu_index_set_column(sgpu_index* idx, uint32_t slot, uint32_t type, const void* values, uint64_t n);
+sgpu_status sgpu_index_get_column(const sgpu_index* idx, uint32_t slot, uint32_t* type, const void** values, uint64_t* n);
+
+/* Column filter: the must / must-not / should shape of the term filter over column predicates.
+ * A RANGE clause MATCHES document d iff lo <= v[d] && v[d] <= hi, in the order of the column's type: unsigned for U32,
+ * two's complement for I32, the IEEE comparison of f32 for F32 (lo_bits / hi_bits are the bounds' bit patterns in that
+ * type). An IN clause matches iff v[d] equals one of set_values[set_begin .. set_begin + set_count) under the same
+ * comparison; the values need not be sorted or distinct, clauses may share them, and set_count == 0 matches nothing.
+ *  - F32: a stored NaN matches no RANGE and no IN clause; -0.0 equals +0.0; +-INFINITY are valid bounds.
+ *  - lo > hi gives a clause that matches nothing; it is not an error.
+ * The set: A = { d < n_docs : every MUST clause matches d, no MUST_NOT clause matches d, and the number of SHOULD
+ * clauses that match d is >= min_should }, intersected with `within`'s set when `within` is not NULL. The corner cases
+ * are the term filter's: n_clauses == 0 gives all documents (of `within`); min_should above the number of SHOULD
+ * clauses gives the empty set; SHOULD is counted per clause (two SHOULD clauses on one slot count on their own); with
+ * no MUST clause and min_should == 0, A is the complement of the MUST_NOT matches.
+ * The result is an ordinary sgpu_filter of `idx`: sgpu_filter_count is the number of matching documents, every filtered
+ * call takes it, and it stays valid when the columns change later (it is a bitmap).
+ * Checks, in this order: (1) NULL idx or out, NULL clauses with n_clauses > 0, NULL set_values with n_set_values > 0:
+ * SGPU_EINVAL; (2) an occur outside 0..2, an op outside 0..1, a slot >= SGPU_MAX_COLUMNS or without a column, a NaN
+ * bound (RANGE) or a NaN set value (IN) on an F32 column, set_begin + set_count > n_set_values (IN): SGPU_EINVAL, the
+ * message names the first offending clause; (3) n_clauses > 64 or n_set_values > 8192: SGPU_ELIMIT; (4) a `within` of
+ * another index: SGPU_EINVAL; (5, device call only) index not uploaded or replica out of range: SGPU_EDEVICE; device
+ * memory: SGPU_ENOMEM, and the index stays usable.
+ * sgpu_filter_create_columns_host needs no upload, scans the host columns with num_threads threads (0 = all) and
+ * DEFINES the words; sgpu_filter_create_columns returns the same words, computed by one kernel on the device of
+ * `replica` and copied (n_docs / 8 bytes) to the host. The column calls of a replica (this one and sgpu_facet_counts)
+ * run on a stream of their own under one mutex: they take turns; searches and the other calls run beside them. */
+enum { SGPU_COLOP_RANGE = 0, SGPU_COLOP_IN = 1 };
+typedef struct sgpu_column_clause {
+  uint32_t slot;      /* a set column */
+  uint32_t occur;     /* SGPU_TERM_MUST / _MUST_NOT / _SHOULD */
+  uint32_t op;        /* SGPU_COLOP_* */
+  uint32_t lo_bits;   /* RANGE: lower bound, bit pattern of the column's type */
+  uint32_t hi_bits;   /* RANGE: upper bound */
+  uint32_t set_begin; /* IN: the clause's values are set_values[set_begin .. set_begin + set_count) */
+  uint32_t set_count;
+  uint32_t reserved;  /* 0 */
+} sgpu_column_clause;
+sgpu_status sgpu_filter_create_columns(sgpu_index* idx, uint32_t replica, const sgpu_column_clause* clauses,
+                                       uint32_t n_clauses, uint32_t min_should, const uint32_t* set_values,
+                                       uint32_t n_set_values, const sgpu_filter* within, sgpu_filter** out);
+sgpu_status sgpu_filter_create_columns_host(sgpu_index* idx, const sgpu_column_clause* clauses, uint32_t n_clauses,
+                                            uint32_t min_should, const uint32_t* set_values, uint32_t n_set_values,
+                                            const sgpu_filter* within, uint32_t num_threads, sgpu_filter** out);
+
+/* Facet counts: over the documents of `filter` (NULL: all documents), the t values of the U32 column `slot` held by
+ * the most documents, by (count descending, value ascending). Only values with a non-zero count are listed.
+ * *out_n = min(t, distinct); *out_distinct = the number of values with a non-zero count; *out_docs = the number of
+ * documents counted (|filter|, or n_docs). out_values and out_counts have room for t entries; rows past *out_n are
+ * written as zero.
+ * Checks, in this order: (1) NULL idx or a NULL output, t outside 1..1024, slot >= SGPU_MAX_COLUMNS or empty, a column
+ * that is not U32: SGPU_EINVAL; (2) a filter of another index: SGPU_EINVAL; (3) a column whose recorded maximum is
+ * >= 1 << 22 = 4194304: SGPU_ELIMIT (the message names the limit); (4, device call only) index not uploaded or replica
+ * out of range: SGPU_EDEVICE; device memory: SGPU_ENOMEM, and the index stays usable.
+ * Counts are integers: the device result equals the host twin's exactly. sgpu_facet_counts_host needs no upload and
+ * DEFINES the rows. The device call uploads the filter's host words for the call (n_docs / 8 bytes), counts in a
+ * table of max + 1 u32 bins (at most 16 MiB, recycled) and selects on the device; it runs on the column calls' stream. */
+sgpu_status sgpu_facet_counts(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter, uint32_t t,
+                              uint32_t* out_values, uint64_t* out_counts, uint32_t* out_n, uint64_t* out_distinct,
+                              uint64_t* out_docs);
+sgpu_status sgpu_facet_counts_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t t,
+                                   uint32_t num_threads, uint32_t* out_values, uint64_t* out_counts, uint32_t* out_n,
+                                   uint64_t* out_distinct, uint64_t* out_docs);
 
 /* ---- scores of caller-given documents ----------------------------------------
  * "What does THIS document score for THIS query?": reranking the candidates of another retriever, fusing candidate

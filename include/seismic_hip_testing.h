@@ -93,6 +93,14 @@ sgpu_status sgpu_debug_exact_launches(sgpu_index* idx, uint32_t replica, uint32_
  * build of the replica's exact file, the file's bytes, its ranges of 32768 documents = workgroups of the kernel}.
  * SGPU_EINVAL before the replica has an exact file */
 sgpu_status sgpu_debug_term_filter_stats(sgpu_index* idx, uint32_t replica, double* out4);
+/* the column calls of `replica`: out8 = {kernel ms of the last sgpu_filter_create_columns launch, kernel ms of the last
+ * sgpu_facet_counts call (its count and select kernels together; HIP events), grid of the filter kernel, grid of the facet
+ * count kernel, documents per workgroup of the filter kernel (a constant: 8192), documents per workgroup of the facet count
+ * kernel, the facet path that ran (0 = LDS histograms, 1 = global atomics), bytes of the replica's column copies}.
+ * SGPU_EINVAL before the replica's first column call */
+sgpu_status sgpu_debug_column_stats(sgpu_index* idx, uint32_t replica, double* out8);
+/* out2 = {count kernel ms, select kernel ms} of the last sgpu_facet_counts call on `replica`: the two parts of out8[1] above */
+sgpu_status sgpu_debug_facet_kernel_ms(sgpu_index* idx, uint32_t replica, double* out2);
 /* the posting arrays a search on `replica` walks, read back from the device: the replica's own (filter == NULL) or those of
  * the filter's view there, which is obtained as a search obtains it - built on first use or after a new upload or graph,
  * under the filter's mutex; no second build path. sizes5 = {block starts (n_blocks + 1), postings, kNN ids (0: no graph),

@@ -85,6 +85,24 @@ class TermClause(C.Structure):
     ]
 
 
+SGPU_COL_U32, SGPU_COL_I32, SGPU_COL_F32 = 0, 1, 2
+SGPU_MAX_COLUMNS = 16
+SGPU_COLOP_RANGE, SGPU_COLOP_IN = 0, 1
+
+
+class ColumnClause(C.Structure):
+    _fields_ = [
+        ("slot", C.c_uint32),
+        ("occur", C.c_uint32),
+        ("op", C.c_uint32),
+        ("lo_bits", C.c_uint32),
+        ("hi_bits", C.c_uint32),
+        ("set_begin", C.c_uint32),
+        ("set_count", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_float),

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from ._abi import (ABI_VERSION, BuildConfig, IndexDesc, LaunchStats, SearchParams, SynthSpec,
-                   SGPU_OK)
+                   SGPU_COL_F32, SGPU_COL_I32, SGPU_COL_U32, SGPU_OK)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGPU_LIB") or os.path.join(_HERE, "libseismic_hip.so")   # SGPU_LIB: experiment builds
@@ -76,6 +76,14 @@ def lib():
         L.sgpu_filter_create.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
         L.sgpu_filter_create_terms.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
         L.sgpu_filter_create_terms_host.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.POINTER(vp)]
+        L.sgpu_index_set_column.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64]
+        L.sgpu_index_get_column.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.sgpu_filter_create_columns.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(vp)]
+        L.sgpu_filter_create_columns_host.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(vp)]
+        L.sgpu_facet_counts.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.sgpu_facet_counts_host.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.sgpu_filter_get_bits.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.sgpu_filter_count.argtypes = [vp]
         L.sgpu_filter_count.restype = C.c_uint64
@@ -306,6 +314,72 @@ class NativeIndex:
         else:
             check(lib().sgpu_filter_create_terms(self.h, int(replica), _p(cl), len(cl), int(min_should), wh, C.byref(h)))
         return NativeFilter._adopt(self, h)
+
+    # ---- document columns: range and set filters, facet counts ----
+    def set_column(self, slot, values, dtype=None):
+        """sgpu_index_set_column: one 32-bit value per document in slot `slot` (0..15), in the index's document order.
+        The column's type follows `dtype`, or the array's: unsigned -> U32, signed -> I32, floating -> F32 (a bare list
+        of Python ints is U32). values=None drops the column."""
+        if values is None:
+            check(lib().sgpu_index_set_column(self.h, int(slot), 0, None, 0))
+            return
+        a = column_array(values, dtype)
+        check(lib().sgpu_index_set_column(self.h, int(slot), COLUMN_KINDS[a.dtype.kind][0], _p(a), len(a)))
+
+    def get_column(self, slot):
+        """sgpu_index_get_column: a copy of the column in `slot` with its type's dtype (uint32 / int32 / float32, the
+        stored bits unchanged), or None for an empty slot."""
+        t, ptr, n = C.c_uint32(0), C.c_void_p(), C.c_uint64(0)
+        check(lib().sgpu_index_get_column(self.h, int(slot), C.byref(t), C.byref(ptr), C.byref(n)))
+        if not ptr.value and n.value == 0:
+            return None
+        raw = np.ctypeslib.as_array((C.c_uint32 * n.value).from_address(ptr.value)).copy() if n.value else np.zeros(0, np.uint32)
+        return raw.view(COLUMN_DTYPES[int(t.value)])
+
+    def make_column_filter(self, clauses, min_should=0, set_values=(), within=None, replica=0, host=False, num_threads=0):
+        """A column filter (sgpu_filter_create_columns[_host]): `clauses` are (slot, occur, op, lo_bits, hi_bits, set_begin,
+        set_count) rows or an array of COLUMN_CLAUSE_DTYPE, `set_values` the u32 bit patterns the IN clauses point into.
+        within: a NativeFilter to intersect with. host=False: one kernel on the device of `replica`; host=True: the host
+        twin that defines the words."""
+        cl = column_clauses(clauses)
+        sv = np.ascontiguousarray(set_values, np.uint32)
+        wh = None if within is None else _filter_handle(within)
+        h = C.c_void_p()
+        if host:
+            check(lib().sgpu_filter_create_columns_host(self.h, _p(cl), len(cl), int(min_should), _p(sv), len(sv), wh,
+                                                        int(num_threads), C.byref(h)))
+        else:
+            check(lib().sgpu_filter_create_columns(self.h, int(replica), _p(cl), len(cl), int(min_should), _p(sv), len(sv), wh,
+                                                   C.byref(h)))
+        return NativeFilter._adopt(self, h)
+
+    def facet_counts(self, slot, filter=None, t=10, replica=0, host=False, num_threads=0):
+        """sgpu_facet_counts[_host]: the t most frequent values of the U32 column `slot` among the filter's documents
+        (None: all), by (count descending, value ascending). Returns (values u32 [n], counts u64 [n], distinct, docs)."""
+        t = int(t)
+        if not 0 <= t <= 0xffffffff:
+            raise ValueError("t = %r out of range" % t)
+        vals, cnts = np.zeros(max(t, 1), np.uint32), np.zeros(max(t, 1), np.uint64)
+        n, distinct, docs = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        fh = None if filter is None else _filter_handle(filter)
+        if host:
+            check(lib().sgpu_facet_counts_host(self.h, int(slot), fh, t, int(num_threads), _p(vals), _p(cnts), C.byref(n),
+                                               C.byref(distinct), C.byref(docs)))
+        else:
+            check(lib().sgpu_facet_counts(self.h, int(replica), int(slot), fh, t, _p(vals), _p(cnts), C.byref(n),
+                                          C.byref(distinct), C.byref(docs)))
+        if vals[n.value:t].any() or cnts[n.value:t].any():
+            raise RuntimeError("facet rows past out_n are not zero")
+        return vals[:n.value], cnts[:n.value], int(distinct.value), int(docs.value)
+
+    def debug_column_stats(self, replica=0):
+        """sgpu_debug_column_stats (test hook): what the last column calls on `replica` measured."""
+        out = np.zeros(8, np.float64)
+        fn = lib().sgpu_debug_column_stats
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        check(fn(self.h, int(replica), _p(out)))
+        return dict(filter_ms=float(out[0]), facet_ms=float(out[1]), filter_grid=int(out[2]), facet_grid=int(out[3]),
+                    filter_docs_per_wg=int(out[4]), facet_docs_per_wg=int(out[5]), facet_path=int(out[6]), column_bytes=int(out[7]))
 
     def debug_posting_view(self, replica=0, filter=None):
         """sgpu_debug_posting_view (a test hook: needs SGPU_TEST_HOOKS=1): the posting arrays a search on `replica` walks,
@@ -749,6 +823,45 @@ def term_clauses(clauses):
         if not 0 <= int(c) <= 0xffffffff or not 0 <= int(occur) <= 0xffffffff:
             raise ValueError("clause %d: component %r / occur %r out of range" % (i, c, occur))
         out[i] = (int(c), int(occur), w, 0)
+    return out
+
+
+COLUMN_CLAUSE_DTYPE = np.dtype([("slot", np.uint32), ("occur", np.uint32), ("op", np.uint32), ("lo_bits", np.uint32),
+                                ("hi_bits", np.uint32), ("set_begin", np.uint32), ("set_count", np.uint32),
+                                ("reserved", np.uint32)])   # sgpu_column_clause
+COLUMN_DTYPES = {SGPU_COL_U32: np.uint32, SGPU_COL_I32: np.int32, SGPU_COL_F32: np.float32}
+COLUMN_KINDS = {"u": (SGPU_COL_U32, np.uint32), "b": (SGPU_COL_U32, np.uint32), "i": (SGPU_COL_I32, np.int32),
+                "f": (SGPU_COL_F32, np.float32)}   # numpy dtype kind -> (column type, stored dtype)
+
+
+def column_array(values, dtype=None):
+    """The values of a column as a contiguous 1-d array of its stored dtype (uint32 / int32 / float32): the type follows
+    `dtype`, or the values' - unsigned -> u32, signed -> i32, floating -> f32; Python ints without a negative one are u32.
+    An integer that the stored dtype cannot hold raises ValueError."""
+    a = np.asarray(values, dtype)
+    kind = a.dtype.kind
+    if dtype is None and not isinstance(values, np.ndarray) and kind == "i" and (a.size == 0 or int(a.min()) >= 0):
+        kind = "u"
+    if kind not in COLUMN_KINDS:
+        raise TypeError("a column holds unsigned, signed or floating values, got dtype %s" % a.dtype)
+    cdt = COLUMN_KINDS[kind][1]
+    if kind != "f" and a.size and (int(a.min()) < np.iinfo(cdt).min or int(a.max()) > np.iinfo(cdt).max):
+        raise ValueError("column values do not fit %s" % np.dtype(cdt).name)
+    return np.ascontiguousarray(a.ravel(), cdt)
+
+
+def column_clauses(clauses):
+    """(slot, occur, op, lo_bits, hi_bits, set_begin, set_count) rows, or an array of COLUMN_CLAUSE_DTYPE -> a contiguous
+    array of sgpu_column_clause."""
+    if isinstance(clauses, np.ndarray) and clauses.dtype == COLUMN_CLAUSE_DTYPE:
+        return np.ascontiguousarray(clauses)
+    rows = list(clauses)
+    out = np.zeros(len(rows), COLUMN_CLAUSE_DTYPE)
+    for i, row in enumerate(rows):
+        row = tuple(int(x) for x in row)
+        if len(row) != 7 or any(not 0 <= x <= 0xffffffff for x in row):
+            raise ValueError("clause %d: seven fields of 32 bits, got %r" % (i, row))
+        out[i] = row + (0,)
     return out
 
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "call_cut.hpp"
+#include "columns.hpp"
 #include "device_calls.hpp"
 #include "filter.hpp"
 #include "host_index.hpp"
@@ -108,6 +109,11 @@ static void drop_replicas(sgpu_index* idx) {
   idx->exact.clear();
   for (ScoreState* s : idx->score) score_state_free(s);
   idx->score.clear();
+  {   // (the column copies of the replicas that go; the host columns stay, and the next column call copies them again)
+    std::lock_guard<std::mutex> lk(idx->column_mu);
+    for (ColumnState* s : idx->column_state) column_state_free(s);
+    idx->column_state.clear();
+  }
   for (DeviceIndex* d : idx->replicas) device_index_free(d);
   idx->replicas.clear();
   idx->dev = nullptr;
@@ -183,7 +189,14 @@ sgpu_status sgpu_index_build_knn(sgpu_index* idx, uint32_t nknn) {
   }
 }
 
-uint64_t sgpu_index_device_bytes(const sgpu_index* idx) { return idx ? device_index_bytes(idx->dev) : 0; }
+uint64_t sgpu_index_device_bytes(const sgpu_index* idx) { return idx ? device_index_bytes(idx->dev) + column_device_bytes(idx) : 0; }
+
+sgpu_status sgpu_index_set_column(sgpu_index* idx, uint32_t slot, uint32_t type, const void* values, uint64_t n) {
+  return column_set(idx, slot, type, values, n);
+}
+sgpu_status sgpu_index_get_column(const sgpu_index* idx, uint32_t slot, uint32_t* type, const void** values, uint64_t* n) {
+  return column_get(idx, slot, type, values, n);
+}
 
 sgpu_status sgpu_index_stream_stats(const sgpu_index* idx, uint64_t* raw_docs, uint64_t* raw_elements) {
   if (!idx || !raw_docs || !raw_elements) return fail(SGPU_EINVAL, "null argument");
@@ -485,6 +498,25 @@ sgpu_status sgpu_filter_create_terms(sgpu_index* idx, uint32_t replica, const sg
 sgpu_status sgpu_filter_create_terms_host(sgpu_index* idx, const sgpu_term_clause* clauses, uint32_t n_clauses, uint32_t min_should,
                                           const sgpu_filter* within, uint32_t num_threads, sgpu_filter** out) {
   return term_filter_host(idx, clauses, n_clauses, min_should, within, num_threads, out);
+}
+sgpu_status sgpu_filter_create_columns(sgpu_index* idx, uint32_t replica, const sgpu_column_clause* clauses, uint32_t n_clauses,
+                                       uint32_t min_should, const uint32_t* set_values, uint32_t n_set_values, const sgpu_filter* within,
+                                       sgpu_filter** out) {
+  return column_filter_device(idx, replica, clauses, n_clauses, min_should, set_values, n_set_values, within, out);
+}
+sgpu_status sgpu_filter_create_columns_host(sgpu_index* idx, const sgpu_column_clause* clauses, uint32_t n_clauses, uint32_t min_should,
+                                            const uint32_t* set_values, uint32_t n_set_values, const sgpu_filter* within,
+                                            uint32_t num_threads, sgpu_filter** out) {
+  return column_filter_host(idx, clauses, n_clauses, min_should, set_values, n_set_values, within, num_threads, out);
+}
+sgpu_status sgpu_facet_counts(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter, uint32_t t,
+                              uint32_t* out_values, uint64_t* out_counts, uint32_t* out_n, uint64_t* out_distinct, uint64_t* out_docs) {
+  return facet_counts_device(idx, replica, slot, filter, t, out_values, out_counts, out_n, out_distinct, out_docs);
+}
+sgpu_status sgpu_facet_counts_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t t, uint32_t num_threads,
+                                   uint32_t* out_values, uint64_t* out_counts, uint32_t* out_n, uint64_t* out_distinct,
+                                   uint64_t* out_docs) {
+  return facet_counts_host(idx, slot, filter, t, num_threads, out_values, out_counts, out_n, out_distinct, out_docs);
 }
 sgpu_status sgpu_filter_get_bits(const sgpu_filter* filter, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words) {
   return filter_get_bits(filter, out_words, cap_words, n_words);

@@ -9,6 +9,7 @@
 
 #include "../../include/seismic_hip_testing.h"
 #include "call_cut.hpp"
+#include "columns.hpp"
 #include "device_calls.hpp"
 #include "filter.hpp"
 #include "host_index.hpp"
@@ -212,6 +213,21 @@ sgpu_status sgpu_debug_term_filter_stats(sgpu_index* idx, uint32_t replica, doub
   if (!idx || !out4) return fail(SGPU_EINVAL, "null argument");
   if (!term_filter_debug_stats(idx, replica, out4)) return fail(SGPU_EINVAL, "replica %u has no exact file", replica);
   return SGPU_OK;
+}
+
+// (not part of the boundary: the column calls of `replica` - out8 = {kernel ms of the last column-filter launch, kernel ms of the
+// last facet call, the grid of each, the documents per workgroup of each, the facet path (0 LDS, 1 global), bytes of the
+// replica's column copies}; SGPU_EINVAL before the replica's first column call. tools/column_probe.py)
+sgpu_status sgpu_debug_column_stats(sgpu_index* idx, uint32_t replica, double* out8) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  return last_call(column_debug_stats, idx, replica, out8, "column");
+}
+
+// (not part of the boundary: {count kernel ms, select kernel ms} of the last sgpu_facet_counts call on `replica` - the two
+// parts of out8[1] above; SGPU_EINVAL before the replica's first column call. tools/column_probe.py)
+sgpu_status sgpu_debug_facet_kernel_ms(sgpu_index* idx, uint32_t replica, double* out2) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  return last_call(facet_debug_kernel_ms, idx, replica, out2, "column");
 }
 
 // (not part of the boundary: device and wall milliseconds of the build of the filter's view on `replica`; SGPU_EINVAL

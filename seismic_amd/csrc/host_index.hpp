@@ -12,6 +12,16 @@ namespace sgpu {
 struct DeviceIndex;  // device_index.hpp
 struct ExactFile;    // exact_file.hpp
 struct ScoreState;   // score_state.hpp
+struct ColumnState;  // columns.hpp
+
+// One document column (sgpu_index_set_column): the host copy, and which set_column call made it - a replica's device copy
+// remembers the generation it was made from (columns.hpp). generation == 0: the slot is empty.
+struct HostColumn {
+  uint32_t type = 0;
+  uint32_t max_u32 = 0;   // U32 columns: the largest value
+  uint64_t generation = 0;
+  std::vector<uint32_t> values;
+};
 
 struct HostIndex {
   uint32_t comp_width = 2;
@@ -245,4 +255,10 @@ struct sgpu_index {
   // bumped by every call that replaces device state a filter's views derive from (upload, upload_many, set_knn,
   // build_knn): a view built under an older generation is rebuilt on its next use, never dereferenced (filter.hip)
   std::atomic<uint64_t> generation{0};
+  // document columns (columns.hpp): not part of the index file; column_mu guards the creation of the replicas' states and,
+  // together with every state's own mutex, the replacement of a column
+  sgpu::HostColumn columns[SGPU_MAX_COLUMNS];
+  uint64_t column_generation = 0;
+  std::vector<sgpu::ColumnState*> column_state;   // per replica (null until its first column call)
+  std::mutex column_mu;
 };

@@ -40,7 +40,7 @@ import tarfile
 import numpy as np
 
 from . import _native
-from ._abi import BuildConfig
+from ._abi import SGPU_COLOP_IN, SGPU_COLOP_RANGE, SGPU_MAX_COLUMNS, BuildConfig
 
 MAX_TOKEN_LEN = 30
 
@@ -272,6 +272,38 @@ def _term_filter(owner, component_of, must, must_not, should, min_should, min_we
     if not host:
         owner._ensure_device()
     return SeismicFilter(owner, owner._ix.make_term_filter(clauses, min_should, None if within is None else within._f, host=host))
+
+
+def _column_bounds(dt, lo, hi):
+    """(lo, hi) of a range entry -> the bounds' bit patterns in the column's dtype; None: the type's lowest / highest
+    value. A bound outside an integer type's range is moved to its nearest value, or the clause made one that matches
+    nothing (lo > hi) where the range lies outside the type."""
+    if dt == np.float32:
+        lo = -np.inf if lo is None else lo
+        hi = np.inf if hi is None else hi
+    else:
+        info = np.iinfo(dt)
+        lo = info.min if lo is None or lo == -np.inf else lo
+        hi = info.max if hi is None or hi == np.inf else hi
+        if lo != lo or hi != hi:
+            raise ValueError("a bound is NaN")
+        if lo > info.max or hi < info.min:
+            lo, hi = 1, 0
+        lo, hi = max(int(np.ceil(lo)), info.min), min(int(np.floor(hi)), info.max)
+    b = np.array([lo, hi], dt).view(np.uint32)
+    return int(b[0]), int(b[1])
+
+
+def _column_set(dt, values):
+    """The values of a set entry -> their bit patterns in the column's dtype; a value the type cannot hold matches nothing
+    and is dropped."""
+    v = np.asarray(list(values) if not isinstance(values, np.ndarray) else values).ravel()
+    if dt != np.float32 and v.size:
+        info = np.iinfo(dt)
+        if v.dtype.kind == "f":
+            v = v[np.isfinite(v) & (v == np.floor(v))]
+        v = np.asarray([int(x) for x in v if info.min <= int(x) <= info.max], np.int64)
+    return v.astype(dt).view(np.uint32).tolist()
 
 
 # ---------------------------------------------------------------------------
@@ -517,15 +549,109 @@ class _ScoreMixin:
             raise ValueError("a group key is a u32")
         self._groups = (keys.astype(np.uint32), known)
 
-    def batch_collapse(self, query_components, query_values, doc_ids_per_query, groups_per_query, k, m=1, device=None):
+    # ---- document columns (sgpu_index_set_column, sgpu_filter_create_columns, sgpu_facet_counts) ----
+    def set_column(self, name, values, dtype=None):
+        """A per-document attribute of 32 bits, held with the index on host and device (not saved with it): an array with
+        one value per document in the index's order, or a dict document id -> value (an id the index does not hold
+        raises ValueError; documents that are not named get 0). The column's type follows `dtype`, or the values':
+        unsigned -> u32, signed -> i32, floating -> f32; Python ints without a negative one are u32. Setting a name
+        again replaces the column; None drops it. At most 16 names at a time (ValueError)."""
+        slots = self.__dict__.setdefault("_columns", {})
+        if values is None:
+            if name in slots:
+                self._ix.set_column(slots.pop(name)[0], None)
+            return
+        if name in slots:
+            slot = slots[name][0]
+        else:
+            free = [s for s in range(SGPU_MAX_COLUMNS) if s not in {v[0] for v in slots.values()}]
+            if not free:
+                raise ValueError("set_column: %d columns are set already; drop one first" % SGPU_MAX_COLUMNS)
+            slot = free[0]
+        n = int(self.len)
+        if isinstance(values, dict):
+            try:
+                rows = self._score_rows(list(values.keys()))
+            except KeyError as e:
+                raise ValueError("set_column: unknown document id %s" % (e,))
+            given = _native.column_array(list(values.values()), dtype)
+            col = np.zeros(n, given.dtype)
+            col[rows] = given
+        else:
+            col = _native.column_array(values, dtype).ravel()
+            if len(col) != n:
+                raise ValueError("%d column values for %d documents" % (len(col), n))
+        self._ix.set_column(slot, col)
+        slots[name] = (slot, self._ix.get_column(slot).dtype)
+
+    def _column(self, name):
+        slots = getattr(self, "_columns", None) or {}
+        if name not in slots:
+            raise ValueError("no column %r: call set_column first" % (name,))
+        return slots[name]
+
+    def make_column_filter(self, must=(), must_not=(), should=(), min_should=0, within=None, device=None):
+        """A SeismicFilter of the documents whose columns satisfy every `must` entry, no `must_not` entry and at least
+        `min_should` of the `should` entries (sgpu_filter_create_columns). An entry is (name, lo, hi): lo <= value <= hi in
+        the column's own order, None as a bound meaning the type's lowest or highest value (-inf / +inf for f32); or
+        (name, [values]): the value is one of them. A stored NaN matches nothing; -0.0 equals +0.0. within: a
+        SeismicFilter to intersect with. device None: the GPU when the index is uploaded, else the host cores; False:
+        the host; an int: the GPU. count is the number of matching documents."""
+        clauses, set_values = [], []
+        for occur, entries in ((0, must), (1, must_not), (2, should)):   # SGPU_TERM_MUST, _MUST_NOT, _SHOULD
+            if isinstance(entries, tuple) and entries and isinstance(entries[0], str):
+                raise TypeError("must / must_not / should take an iterable of entries, not a single entry")
+            for e in entries:
+                e = tuple(e)
+                slot, dt = self._column(e[0])
+                if len(e) == 3:
+                    lo, hi = _column_bounds(dt, e[1], e[2])
+                    clauses.append((slot, occur, SGPU_COLOP_RANGE, lo, hi, 0, 0))
+                elif len(e) == 2:
+                    vals = _column_set(dt, e[1])
+                    clauses.append((slot, occur, SGPU_COLOP_IN, 0, 0, len(set_values), len(vals)))
+                    set_values.extend(vals)
+                else:
+                    raise ValueError("an entry is (name, lo, hi) or (name, [values]), got %r" % (e,))
+        if within is not None and not isinstance(within, SeismicFilter):
+            raise TypeError("within= takes a SeismicFilter")
+        if within is not None and within.index is not self:
+            raise ValueError("the filter was made on another index")
+        host = device is False or (device is None and not self._uploaded)
+        if not host:
+            self._ensure_device()
+        return SeismicFilter(self, self._ix.make_column_filter(clauses, min_should, np.asarray(set_values, np.uint32),
+                                                               None if within is None else within._f, host=host))
+
+    def facets(self, name, filter=None, top=10, device=None):
+        """Facet counts -> ([(value, count)], distinct, docs): the `top` (1 .. 1024) most frequent values of the u32 column
+        `name` among the filter's documents (None: all), by count descending, value ascending; `distinct` is the number
+        of values that occur, `docs` the number of documents counted (sgpu_facet_counts). device as for
+        make_column_filter."""
+        slot, dt = self._column(name)
+        host = device is False or (device is None and not self._uploaded)
+        if not host:
+            self._ensure_device()
+        vals, cnts, distinct, docs = self._ix.facet_counts(slot, _native_filter(self, filter), top, host=host)
+        return list(zip(vals.tolist(), cnts.tolist())), distinct, docs
+
+    def batch_collapse(self, query_components, query_values, doc_ids_per_query, groups_per_query, k, m=1, device=None, groups=None):
         """Field collapsing -> [[(group, score, best_doc_id, best_score, members)]]: per query the k (1 .. 1024) best
         groups of its candidates (as for batch_score, at most 4096 per query). groups_per_query[q][i] is the u32 group
-        key of candidate i of query q; None: the keys set_groups holds. A group's members are its distinct documents,
+        key of candidate i of query q; None: the keys set_groups holds or, with groups="name", the values of that u32
+        column (set_column). A group's members are its distinct documents,
         best first; its score is the f32 sum of its first m (1 .. 64) members in that order (m = 1: MaxP); groups come
         by score descending, key ascending. sgpu_collapse_documents on the GPU the index is on (device None) or its
         host twin (device False)."""
         off, comps, vals, cand_off, cand, rows = self._score_csr(query_components, query_values, doc_ids_per_query)
-        if groups_per_query is None:
+        if groups is not None:
+            if groups_per_query is not None:
+                raise ValueError("pass groups_per_query or groups=, not both")
+            slot, dt = self._column(groups)
+            if dt != np.uint32:
+                raise ValueError("groups=%r: group keys come from a u32 column, this one is %s" % (groups, dt))
+            grp = self._ix.get_column(slot)[cand.astype(np.int64)]
+        elif groups_per_query is None:
             table = getattr(self, "_groups", None)
             if table is None:
                 raise ValueError("no group keys: pass groups_per_query or call set_groups first")
@@ -881,16 +1007,19 @@ class _IndexBase(_ScoreMixin):
                                  query_cut, heap_factor, n_knn=n_knn, sorted=sorted, filter=filter)
 
     def batch_search_collapsed(self, queries_ids, query_components, query_values, k, query_cut, heap_factor, depth=100, m=1,
-                               n_knn=0, sorted=True, filter=None):
+                               n_knn=0, sorted=True, filter=None, groups=None):
         """Search, then collapse -> [[(query_id, group, score, best_doc_id, best_score, members)]]: batch_search for `depth`
-        hits per query, batch_collapse of every query's hits under the keys set_groups holds, cut to k groups.
+        hits per query, batch_collapse of every query's hits under the keys set_groups holds (or, with groups="name", the
+        values of that u32 column), cut to k groups.
         Composition of the two calls, nothing else."""
-        if getattr(self, "_groups", None) is None:
+        if groups is not None:
+            self._column(groups)
+        elif getattr(self, "_groups", None) is None:
             raise ValueError("no group keys: call set_groups first")
         hits = self.batch_search(queries_ids, query_components, query_values, depth, query_cut, heap_factor, n_knn=n_knn,
                                  sorted=sorted, filter=filter)
         docs = [[d for _, _, d in row] for row in hits]
-        rows = self.batch_collapse(query_components, query_values, docs, None, k, m)
+        rows = self.batch_collapse(query_components, query_values, docs, None, k, m, groups=groups)
         qids = [str(x) for x in np.asarray(queries_ids).ravel()]
         return [[(qids[q],) + r for r in row] for q, row in enumerate(rows)]
 
