@@ -35,6 +35,21 @@ sgpu_status sgpu_debug_row_dir(const sgpu_index* idx, uint32_t* out, uint64_t ca
 /* the launch plan of a batch: processing order, out3 = {block dots needed at most, largest first list, largest list} */
 sgpu_status sgpu_debug_plan(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
                             uint32_t nq, uint32_t query_cut, uint32_t* order_out, uint32_t* out3);
+/* the hashed-lookup half of that plan (no device; the same code path as sgpu_debug_plan): *out_hash_ok = 1 when a launch of
+ * this batch may take the hashed query lookup - the index has u32 components, f16 values and dim < 2^24, SGPU_NO_HASH is not
+ * set, and EVERY query has a seed: the first of 64 multipliers that sends its components (at most 1024 of them) to distinct
+ * slots of the 4096-slot table. seeds_out[q], nq words: that seed, 0 ... 63. The search stops at the first query without a
+ * seed: its entry holds 64 & 63 = 0, the entries of the queries after it were never computed and hold 0 as well, and
+ * *out_hash_ok = 0 - the entries before it are real seeds. All entries are 0 where the index is not of that form */
+sgpu_status sgpu_debug_plan_seeds(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
+                                  uint32_t nq, uint32_t query_cut, uint32_t* out_hash_ok, uint32_t* seeds_out);
+/* the kernel variant of the last search launch of a lane of `replica`: lane < 0 its main lane (sgpu_batch_run /
+ * sgpu_batch_run_counted and the calls built on them), else chunk pool lane `lane` (0 ... 7, as sgpu_debug_lane_chunk counts
+ * them). out4 = {query lookup layout: 0 packed / 1 dense / 2 split / 3 hashed, streamed stage 2, cooperative: 0 / 1 / 2
+ * forced, counted pass} - the words [34], [38], [40], [37] of sgpu_debug_launch_config. Recorded once the launch has been
+ * enqueued successfully; a summary-distances (dots) launch and a launch that failed leave the words of the search launch
+ * before it. 0: the lane has launched no search yet, or is serving a call */
+uint32_t sgpu_debug_lane_variant(sgpu_index* idx, uint32_t replica, int32_t lane, uint32_t* out4);
 /* the same plan as the DEVICE computes it for staged chunks (needs an uploaded index; 1 ... 16384 queries, query_cut 1 ... 16) */
 sgpu_status sgpu_debug_device_plan(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals,
                                    uint32_t nq, uint32_t query_cut, uint32_t* order_out, uint32_t* out3);

@@ -201,6 +201,43 @@ def debug_cut_rule(shared, device_plans):
     return int(out[0]), int(out[1])
 
 
+def debug_plan_seeds(index, q_off, comps, vals, query_cut):
+    """(hash_ok, seeds [nq] u32) of the host's launch plan of a batch against `index` (test hook sgpu_debug_plan_seeds, no
+    device): whether a launch may take the hashed query lookup, and every query's seed as the header describes the entries."""
+    q_off, comps, vals = _csr(q_off, comps, vals)
+    nq = len(q_off) - 1
+    ok, seeds = C.c_uint32(0), np.zeros(max(nq, 1), np.uint32)
+    fn = lib().sgpu_debug_plan_seeds
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
+    check(fn(index.h, _p(q_off), _p(comps), _p(vals), nq, int(query_cut), C.byref(ok), _p(seeds)))
+    return int(ok.value), seeds[:nq]
+
+
+def debug_lane_variant(index, lane=-1, replica=0):
+    """dict(lookup, streamed, coop, counted) of the last search launch of a lane of `replica` - its main lane (lane < 0: what
+    DeviceBatch.run / run_counted launch on) or chunk pool lane `lane` - or None where the lane has launched nothing (test
+    hook sgpu_debug_lane_variant)."""
+    out = np.zeros(4, np.uint32)
+    fn = lib().sgpu_debug_lane_variant
+    fn.restype = C.c_uint32
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+    if not fn(index.h, int(replica), int(lane), _p(out)):
+        return None
+    return dict(zip(("lookup", "streamed", "coop", "counted"), (int(x) for x in out)))
+
+
+def debug_lane_chunk(index, lane):
+    """dict(nq, q_base, planned_by, query_cut) of the last chunk pool lane `lane` of replica 0 served (planned_by: 0 the host,
+    1 the device, 2 nobody), or None (test hook sgpu_debug_lane_chunk)."""
+    info = np.zeros(4, np.uint32)
+    fn = lib().sgpu_debug_lane_chunk
+    fn.restype = C.c_uint32
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+    if not fn(index.h, int(lane), _p(info), None, 0):
+        return None
+    return dict(zip(("nq", "q_base", "planned_by", "query_cut"), (int(x) for x in info)))
+
+
 def params(k, query_cut, heap_factor, first_sorted, n_knn=0):
     return SearchParams(k=int(k), query_cut=int(query_cut), heap_factor=float(heap_factor),
                         n_knn=int(n_knn), first_sorted=1 if first_sorted else 0)

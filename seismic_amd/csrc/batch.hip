@@ -291,7 +291,25 @@ sgpu_status configure(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sgpu_sear
   }
   a->queue = b->staged ? b->queue_dev : lane->queue;
   lane->coop_last = a->coop.enabled != 0;
+  lane->variant_next[0] = c.lookup, lane->variant_next[1] = c.streamed, lane->variant_next[2] = c.coop, lane->variant_next[3] = c.counted;
   return SGPU_OK;
+}
+
+// (test hook: the kernel variant of the last search launch of a lane of replica d - the main lane, which the resident batch
+// API runs on, for lane < 0, else chunk pool lane `lane` - out4 = {lookup, streamed, cooperative 0 / 1 / 2 forced, counted}.
+// Recorded next to lane->last once the launch has gone out; a dots launch (summary_distances) does not touch it. Returns 0
+// where the lane has launched no search or is serving a call. sgpu_debug_lane_variant)
+uint32_t debug_lane_variant(DeviceIndex* d, int32_t lane, uint32_t* out4) {
+  if (!d || !out4 || lane >= (int32_t)DeviceIndex::kPool) return 0;
+  const Lane* l = lane < 0 ? &d->main : &d->pool[lane];
+  if (lane >= 0) {
+    std::lock_guard<std::mutex> pool(d->pool_mu);
+    if (l->busy) return 0;
+  }
+  std::lock_guard<std::mutex> lock(d->mu);   // (configure writes the words under it)
+  if (!l->variant_set) return 0;
+  std::memcpy(out4, l->variant, sizeof(l->variant));
+  return 1;
 }
 
 static void drain_events(Lane* l) {   // stream must be idle
@@ -367,6 +385,7 @@ sgpu_status batch_run(DeviceIndex* d, Lane* lane, sgpu_batch* b, const sgpu_sear
     lane->last.grid = a.grid;
     lane->last.block = a.block;
     lane->last.lds_bytes = a.lds_bytes;
+    if (mode != MODE_DOTS) lane->variant_commit();
   }
   if (sync) {
     HIP_TRY(hipStreamSynchronize(lane->stream));

@@ -129,6 +129,26 @@ sgpu_status sgpu_debug_plan(const sgpu_index* idx, const uint64_t* q_off, const 
   return debug_plan(idx->host, q_off, comps, vals, nq, query_cut, order_out, out3);
 }
 
+// (not part of the boundary: the LK_HASH half of the same plan, through the same debug_plan / make_plan - *out_hash_ok = every
+// query has a collision-free seed and the index is of the hashed family (u32 components, f16 values, dim < 2^24, no
+// SGPU_NO_HASH); seeds_out[q] = the query's seed. The search stops at the first query without one: that query's entry is
+// 64 & 63 = 0 and the entries after it were never computed, 0 too; all 0 when the index is not of the family. No device)
+sgpu_status sgpu_debug_plan_seeds(const sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
+                                  uint32_t query_cut, uint32_t* out_hash_ok, uint32_t* seeds_out) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  if (!idx || !q_off || !out_hash_ok || !seeds_out) return fail(SGPU_EINVAL, "null argument");
+  uint32_t out3[3];
+  return debug_plan(idx->host, q_off, comps, vals, nq, query_cut, nullptr, out3, out_hash_ok, seeds_out);
+}
+
+// (not part of the boundary: the kernel variant of the last search launch of a lane of `replica` - lane < 0: its main lane,
+// else chunk pool lane `lane`, as sgpu_debug_lane_chunk counts them - batch.hip debug_lane_variant)
+uint32_t sgpu_debug_lane_variant(sgpu_index* idx, uint32_t replica, int32_t lane, uint32_t* out4) {
+  SGPU_HOOK_OR(0u);
+  if (!idx || !out4 || replica >= idx->replicas.size()) return 0u;
+  return debug_lane_variant(idx->replicas[replica], lane, out4);
+}
+
 // (not part of the boundary: the same plan as the DEVICE computes it for staged chunks - plan_kernel.hip; replica 0)
 sgpu_status sgpu_debug_device_plan(sgpu_index* idx, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                                    uint32_t query_cut, uint32_t* order_out, uint32_t* out3) {

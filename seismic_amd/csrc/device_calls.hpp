@@ -31,7 +31,8 @@ void call_exit(DeviceIndex* d);
 // ---- launch_plan.hip (device_plan_dots takes d->mu itself)
 uint32_t device_plan_dots(DeviceIndex* d, const sgpu_search_params& sp, uint32_t nq, uint32_t cut);
 sgpu_status debug_plan(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
-                       uint32_t query_cut, uint32_t* order_out, uint32_t* out3);
+                       uint32_t query_cut, uint32_t* order_out, uint32_t* out3, uint32_t* hash_ok_out = nullptr,
+                       uint32_t* seeds_out = nullptr);
 sgpu_status debug_device_plan(DeviceIndex* d, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
                               uint32_t query_cut, uint32_t* order_out, uint32_t* out3);
 
@@ -47,6 +48,7 @@ sgpu_status batch_fetch(DeviceIndex* d, Lane* lane, sgpu_batch* b, uint32_t k, f
                         uint32_t* out_n);
 sgpu_status batch_fetch_stats(DeviceIndex* d, sgpu_batch* b, uint32_t* out);
 uint32_t coop_trace_dump(DeviceIndex* d, uint64_t* out, uint32_t cap);
+uint32_t debug_lane_variant(DeviceIndex* d, int32_t lane, uint32_t* out4);
 sgpu_status summary_distances(DeviceIndex* d, const HostIndex& h, uint32_t list, const uint32_t* comps,
                               const float* vals, uint32_t nnz, float* out_dots, uint32_t* out_nb);
 sgpu_status build_knn_on_device(DeviceIndex* d, HostIndex& h, uint32_t nknn);

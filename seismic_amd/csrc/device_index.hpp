@@ -39,6 +39,15 @@ struct Lane {
   double sum_ms = 0;
   uint32_t n_timed = 0;
   sgpu_launch_stats last{};
+  // (test hook sgpu_debug_lane_variant) the kernel variant of the lane's last search launch (MODE_SEARCH / MODE_COUNTED,
+  // not a dots launch): {lookup (LK_*), streamed, cooperative 0 / 1 / 2 forced, counted}. configure leaves what it chose in
+  // variant_next; the launcher copies it to variant once launch_search has succeeded (variant_commit). variant_set: one has
+  uint32_t variant[4] = {0, 0, 0, 0}, variant_next[4] = {0, 0, 0, 0};
+  bool variant_set = false;
+  void variant_commit() {
+    for (int i = 0; i < 4; ++i) variant[i] = variant_next[i];
+    variant_set = true;
+  }
   bool busy = false;
 };
 

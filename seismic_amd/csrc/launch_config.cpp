@@ -201,8 +201,18 @@ sgpu_status launch_configure(const LaunchInput& in, LaunchConfig* out) {
       im = want_items;
       while (im > 512 && o + hash_bytes + uni_for(im) > budget) im -= 128;
     }
-    if (o + hash_bytes + uni_for(im) <= budget) items_max = im;
-    else hashed = false;
+    if (o + hash_bytes + uni_for(im) <= budget) {
+      items_max = im;
+    } else {
+      // Past the budget the hashed table is declined for occupancy's sake - unless it is the ONLY layout the launch can
+      // have: a vocabulary above ~650 000 ids has no packed (8 B per 32 ids) or split (6 B) table inside the LDS limit,
+      // and declining the 32 KB of hashed entries there turned a search that fits (one workgroup per CU) into SGPU_ELIMIT.
+      const bool split_allowed = in.max_nnz <= 65535 && !kn.no_split;
+      const uint64_t fallback_bytes = split_allowed ? split_bytes : bitmap_bytes;
+      const bool fallback_fits = o + fallback_bytes + min_uni <= lds_limit;
+      if (!fallback_fits && o + hash_bytes + uni_for(im) <= lds_limit) items_max = im;
+      else hashed = false;
+    }
   }
   const uint32_t lookup = hashed ? LK_HASH : (dense ? LK_DENSE : (split ? LK_SPLIT : LK_PACKED));
   const uint64_t lookup_bytes = !searching ? 0u : (hashed ? hash_bytes : (dense ? dense_bytes : (split ? split_bytes : bitmap_bytes)));

@@ -115,11 +115,14 @@ sgpu_status make_plan(const DeviceIndex* d, const uint64_t* h_off, const uint32_
 }
 
 // (test hook, no device needed: the launch plan of a batch against a host index - the processing order, the block
-// dots a query needs at most, the largest list walked first / at all. sgpu_debug_plan, tests/test_abi_and_host.py)
+// dots a query needs at most, the largest list walked first / at all. sgpu_debug_plan, tests/test_abi_and_host.py.
+// hash_ok_out / seeds_out, where given: the plan's hash_ok and the second half of its order, one LK_HASH seed per query -
+// sgpu_debug_plan_seeds, tests/test_hash_cases_cpu.py)
 sgpu_status debug_plan(const HostIndex& h, const uint64_t* q_off, const uint32_t* comps, const float* vals, uint32_t nq,
-                       uint32_t query_cut, uint32_t* order_out, uint32_t* out3) {
+                       uint32_t query_cut, uint32_t* order_out, uint32_t* out3, uint32_t* hash_ok_out, uint32_t* seeds_out) {
   DeviceIndex d;
   d.comp_width = h.comp_width;
+  d.value_type = h.value_type;   // (hash_ok asks for it)
   d.view.dim = (uint32_t)h.dim;
   d.list_nb.resize(h.dim);
   d.list_np.resize(h.dim);
@@ -131,7 +134,9 @@ sgpu_status debug_plan(const HostIndex& h, const uint64_t* q_off, const uint32_t
   env_refresh();
   const sgpu_status st = make_plan(&d, q_off, comps, vals, nq, query_cut, &pl);
   if (st != SGPU_OK) return st;
-  for (uint32_t i = 0; i < nq; ++i) order_out[i] = pl.order[i];
+  for (uint32_t i = 0; order_out && i < nq; ++i) order_out[i] = pl.order[i];
+  for (uint32_t i = 0; seeds_out && i < nq; ++i) seeds_out[i] = pl.order[(size_t)nq + i];
+  if (hash_ok_out) *hash_ok_out = pl.hash_ok ? 1u : 0u;
   out3[0] = pl.dots_cap;
   out3[1] = pl.max_nb;
   out3[2] = pl.max_list_nb;

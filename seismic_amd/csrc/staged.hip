@@ -275,6 +275,7 @@ sgpu_status staged_launch(DeviceIndex* d, Lane* lane, uint64_t dim, const uint64
     LaunchArgs a{};
     st = configure(d, lane, b, sp, MODE_SEARCH, &a, view);
     if (st == SGPU_OK) he = launch_search(a);
+    if (st == SGPU_OK && he == hipSuccess) lane->variant_commit();
     if (b->direct_in) {
       if (st == SGPU_OK && he == hipSuccess) lane->queue_pos += nq + a.grid;   // the tickets this launch takes
       else lane->queue_dirty = true;

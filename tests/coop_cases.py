@@ -71,7 +71,7 @@ def knob_env(case, run, block):
     if run.mode == "force":
         env["SGPU_COOP"] = "force"
     if SC.FORMS[case.form] == (4, 0) and "SGPU_FORCE_HASH" not in run.env:
-        env["SGPU_NO_HASH"] = "1"      # (the hashed lookup depends on per-query seeds that no entry point reports)
+        env["SGPU_NO_HASH"] = "1"      # (unforced runs keep the other layouts; the hashed lookup has test_gpu_hash_lookup.py)
     env.update(run.env)
     return env
 

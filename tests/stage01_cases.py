@@ -28,6 +28,7 @@ import functools
 import numpy as np
 
 import coop_cases as CC
+import hash_cases as H
 import model64 as M64
 import orc
 import stream_cases as SC
@@ -84,7 +85,7 @@ def knob_env(case, run, block):
     """The environment a run is launched under: plain (streamed) unless the run asks for SGPU_COOP=force."""
     env = dict(SGPU_BLOCK=str(block), SGPU_COOP="force" if run.coop else "0")
     if SC.FORMS[case.form] == (4, 0) and "SGPU_FORCE_HASH" not in run.env:
-        env["SGPU_NO_HASH"] = "1"      # (the hashed lookup depends on per-query seeds that no entry point reports)
+        env["SGPU_NO_HASH"] = "1"      # (unforced runs keep the other layouts; the hashed lookup has test_gpu_hash_lookup.py)
     env.update(run.env)
     return env
 
@@ -654,8 +655,13 @@ def _check_lookup(case, ix):
     assert L_CYCLE % len(pool) == 0 and L_CYCLE > 2 * 512
     layouts = {}
     for r in case.runs.values():
+        # a forced-hash run is hashed only if EVERY query of its batch has a collision-free seed (hash_cases.py restates the
+        # search): every query of L_POOL has seed 0 here - ids that are multiples of 70 spread well - so no run of this case
+        # falls back and none needs a sibling batch; test_gpu_stage01_edges.py asserts the lookup that ran through the lane hook
+        ok = H.seeds(*case.batch(r)[:2], case.dim, case.cw, case.value_type, "SGPU_NO_HASH" in knob_env(case, r, 512))[0]
+        assert ok == ("SGPU_FORCE_HASH" in r.env), (r.name, ok)
         for block in BLOCKS:
-            h = hook(case, ix, r, block, hash_ok=1 if "SGPU_FORCE_HASH" in r.env else 0)
+            h = hook(case, ix, r, block, hash_ok=ok)
             assert h["lookup"] == r.expect["lookup"], (r.name, block, h["lookup"])
             assert (h["coop"] != 0) == r.coop and (h["streamed"] == 1) == (not r.coop), (r.name, h)
             layouts[r.name] = h["lookup"]

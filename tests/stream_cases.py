@@ -499,7 +499,7 @@ def knob_sets(case, run):
         for block in BLOCKS:
             env = dict(SGPU_COOP="0", SGPU_RING_MAX=str(ring), SGPU_BLOCK=str(block))
             if FORMS[case.form] == (4, 0):
-                env["SGPU_NO_HASH"] = "1"      # (the hashed lookup depends on per-query seeds that no entry point reports)
+                env["SGPU_NO_HASH"] = "1"      # (unforced runs keep the other layouts; the hashed lookup has test_gpu_hash_lookup.py)
             env.update(run.env)
             out.append((ring, block, 512 if run.k > 128 else block, env))
     return out

@@ -5,7 +5,8 @@ max_cand and max_cand + 1, fallbacks in the first and in the second round (the `
 and chunks without a live block, document lengths up to 600 components, helpers that change query and lookup form, a
 workgroup's next query, more than 1024 rounds of one workgroup, kNN refinement behind a wide round, a filtered search. Every run is launched under SGPU_BLOCK in
 {512, 1024} through a resident batch (filtered runs through batch_search): the launch configuration's hook, fed the launch's
-facts, must say cooperative and agree with the launch's own statistics; the rows are the oracle's bit for bit (n, ids in
+facts (hash_ok from sgpu_debug_plan_seeds), must say cooperative and agree with the launch's own statistics and with the
+lane's report of the variant that ran (sgpu_debug_lane_variant); the rows are the oracle's bit for bit (n, ids in
 order, score bits) and pass the float64 model's checkers; for FORCED runs work counter [7] of sgpu_batch_fetch_stats
 (documents scored) equals, query by query, the figure of the restatement in coop_cases.py - the proof that the wide round,
 the fallback or the resume really ran on the device; the same call under SGPU_COOP=0 returns the same rows, which only
@@ -16,12 +17,14 @@ live at their own start, every posting left]); a kNN refinement scores at most n
 No test here forces a wait to give up (codes 1, 2, 3), stalls a role or provokes an abort. Run with `-m gpu`."""
 import ctypes
 import functools
+import os
 
 import numpy as np
 import pytest
 import torch
 
 import coop_cases as CC
+import hash_cases as H
 import stream_cases as SC
 import test_coop_cases_cpu as CPU
 from seismic_amd import _native
@@ -88,25 +91,30 @@ def _cooperative(case, ix, flt, name, run, block, chip, seen):
     rows, stats, counters = _launch(case, ix, flt, run, Q)
     # proof of variant: the hook, fed this launch's facts under this environment, says cooperative, and the launch took
     # that workgroup size and that much LDS
-    facts = SC.plan_facts(case, ix, run, Q)
+    # (hash_ok of this very batch from the host plan's own seed search, equal to the restatement's: hash_cases.py)
+    ok, _ = _native.debug_plan_seeds(ix, *Q, run.cut)
+    assert ok == H.seeds(Q[0], Q[1], case.dim, case.cw, case.value_type, os.environ.get("SGPU_NO_HASH") == "1")[0], (what, ok)
+    facts = dict(SC.plan_facts(case, ix, run, Q), hash_ok=ok)
     hook = _native.debug_launch_config(n_cu=n_cu, max_lds=max_lds, heap_factor=run.hf, **facts)
     if run.k > 256:
         assert hook["coop"] == 0, (what, hook)                       # no cooperative symbol for this k: the plain variant
     else:
         assert (hook["coop"], hook["streamed"]) == (2 if run.mode == "force" else 1, 0), (what, hook)
     assert stats.block == hook["block"], (what, stats.block, hook)
+    # the lane reports the variant that ran: a resident batch launches on the main lane; a filtered run goes through the
+    # entry point, whose first (here: only) chunk takes pool lane 0. The lookup and the counted word are the hook's exactly;
+    # so are streamed and cooperative where the hook was fed the launch's own size (the resident batch)
+    v = _native.debug_lane_variant(ix, 0 if run.filtered else -1)
+    assert v is not None and (v["lookup"], v["counted"]) == (hook["lookup"], hook["counted"]), (what, v, hook)
+    if not run.filtered:
+        assert v == {k_: hook[k_] for k_ in ("lookup", "streamed", "coop", "counted")}, (what, v, hook)
     if "SGPU_FORCE_HASH" in run.env:
-        # the hashed lookup is taken only if every query of the launch has a collision-free seed, which no entry point
-        # reports: the launch's LDS bytes are those of the hook's answer with or without such seeds, and `seen` keeps which
-        with_seeds = _native.debug_launch_config(n_cu=n_cu, max_lds=max_lds, heap_factor=run.hf, **dict(facts, hash_ok=1))
-        assert with_seeds["lookup"] == CPU.LOOKUP["hashed"] != hook["lookup"], (what, with_seeds["lookup"], hook["lookup"])
-        assert stats.lds_bytes in (with_seeds["lds_bytes"], hook["lds_bytes"]), (what, stats.lds_bytes)
-        if with_seeds["lds_bytes"] != hook["lds_bytes"]:
-            seen.setdefault("hashed", []).append(stats.lds_bytes == with_seeds["lds_bytes"])
-    else:
-        # (a filtered run goes through the entry point, which may cut the call into several launches and reports the last
-        # one's statistics: its workgroup size is compared, its LDS bytes are not)
-        assert run.filtered or stats.lds_bytes == hook["lds_bytes"], (what, stats.lds_bytes, hook)
+        # every query of these batches has a seed, so the forced launch IS the hashed one
+        assert ok == 1 and hook["lookup"] == CPU.LOOKUP["hashed"], (what, ok, hook["lookup"])
+    seen.setdefault("hashed", []).append(v["lookup"] == CPU.LOOKUP["hashed"])       # (what the LANE said ran)
+    # (a filtered run goes through the entry point, which may cut the call into several launches and reports the last
+    # one's statistics: its workgroup size is compared, its LDS bytes are not)
+    assert run.filtered or stats.lds_bytes == hook["lds_bytes"], (what, stats.lds_bytes, hook)
     assert stats.n_queries == nq or (run.filtered and 0 < stats.n_queries < nq)
     if run.name == "next_query":
         assert stats.grid < nq and np.gcd(stats.grid, len(run.queries)) == 1, (what, stats.grid)   # every workgroup goes on to a next query

@@ -70,6 +70,11 @@ def test_device_build_laws(seed, law):
 @pytest.mark.parametrize("variant", ["default", "plain"])
 @pytest.mark.parametrize("seed", range(26))
 def test_differential(seed, variant, monkeypatch):
+    differential(seed, variant, monkeypatch)
+
+
+def differential(seed, variant, monkeypatch):
+    """One seed's differential run; returns (index, queries) for callers that look at the launches it made."""
     if variant == "plain":
         monkeypatch.setenv("SGPU_COOP", "0")
     # small batches default to 1024-thread workgroups; odd seeds force the 512-thread configuration
@@ -122,6 +127,7 @@ def test_differential(seed, variant, monkeypatch):
                 assert np.array_equal(gs[i, :n].view(np.uint32), cs[i, :n].view(np.uint32)), (ctx, i)
     finally:
         orc.knn_attach(None, 0)
+    return ix, q
 
 
 def test_long_summary_rows_and_long_queries():

@@ -1,10 +1,13 @@
 """Every query lookup layout returns the oracle's results: the hashed {component id, weight} entries (one LDS
 read per document component; the u32 layout) asked for on the fuzz seeds - seeds with u32 components and f16 values run
 them, the others (u16 components: the hashed families were dropped in r05; fixed-u8 over u32) their own layout -
-512- and 1024-thread workgroups, cooperative and plain launches."""
+512- and 1024-thread workgroups, cooperative and plain launches. The lane hook (sgpu_debug_lane_variant) must report the
+hashed lookup for exactly the seeds whose index has hashed kernels and whose queries all have a seed (hash_cases.seeds)."""
 import pytest
 
-from test_gpu_fuzz import test_differential as _differential
+import hash_cases as H
+from seismic_amd import _native
+from test_gpu_fuzz import differential as _differential
 
 pytestmark = pytest.mark.gpu
 
@@ -14,7 +17,16 @@ def test_hashed_entries_on_the_fuzz_seeds(seed, monkeypatch):
     monkeypatch.setenv("SGPU_FORCE_HASH", "1")
     if seed % 3 == 0:
         monkeypatch.setenv("SGPU_COOP", "force")
-    _differential(seed, "default", monkeypatch)
+    ix, q = _differential(seed, "default", monkeypatch)
+    # which layout the seed's launches took: its 30 queries are one chunk on pool lane 0 of replica 0 (of each replica, for
+    # the seeds with two). The forced hashed lookup is taken exactly when the index has hashed kernels and every query has
+    # a seed - by the restatement (hash_cases.py) and by the host plan's own search, which must agree
+    d = ix.desc
+    ok = H.seeds(q[0], q[1], d.dim, d.comp_width, d.value_type)[0]
+    assert _native.debug_plan_seeds(ix, *q, 4)[0] == ok, (seed, ok)
+    v = _native.debug_lane_variant(ix, 0)
+    assert v is not None and (v["lookup"] == H.LK_HASH) == bool(ok), (seed, ok, v)
+    print("seed %d: comp_width %d value_type %d, every query has a seed: %d, lookup %d" % (seed, d.comp_width, d.value_type, ok, v["lookup"]))
 
 
 @pytest.mark.parametrize("seed", [2, 9, 19])

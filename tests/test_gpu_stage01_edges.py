@@ -5,7 +5,8 @@ over 0 ... 3 rows, list groups at the equality of dots_cap and qg, more streams 
 signs and cuts, the lookup table's clearing between a workgroup's queries under every layout, and sort_first_list around
 the workgroup size. Dots: ix.summary_distances (the kernel's MODE_DOTS) equals orc.summary_distances as uint32 bits under
 SGPU_BLOCK 512 and 1024. Searches: under SGPU_BLOCK 512 and 1024 the launch configuration's hook, fed the launch's facts,
-names the layout, qg, dots_cap, workgroup size and variant the run is there for and agrees with the launch's statistics;
+(hash_ok from sgpu_debug_plan_seeds), names the layout, qg, dots_cap, workgroup size and variant the run is there for and
+agrees with the launch's statistics and with the lane's report of the variant that ran (sgpu_debug_lane_variant);
 the rows are the oracle's bit for bit (n, ids in order, score bits) and pass the float64 model's checkers; the counted pass's
 counters [0..6] equal orc.batch_search_counts per query. test_stage01_cases_cpu.py proves without a device that the cases
 reach their edges. No test here forces an abort code or a fault. Run with `-m gpu`."""
@@ -16,6 +17,7 @@ import pytest
 import torch
 
 import coop_cases as CC
+import hash_cases as H
 import stage01_cases as S
 import stream_cases as SC
 import test_stage01_cases_cpu as CPU
@@ -77,23 +79,27 @@ def test_searches_are_the_oracles_rows_and_counters(name, block):
         nq = len(Q[0]) - 1
         pick = np.arange(nq) % len(run.queries)
         ws, wi, wn, wc = CPU.oracle_counts(name, run.name)
-        with CC.knobs(S.knob_env(case, run, block)):
+        env = S.knob_env(case, run, block)
+        with CC.knobs(env):
             b = _native.DeviceBatch(ix, *Q, run.k)
             stats = b.run(run.k, run.cut, run.hf, run.first_sorted)            # (raises unless SGPU_OK)
             rows = b.fetch(run.k)
-            facts = dict(SC.plan_facts(case, ix, run, Q), n_cu=n_cu, max_lds=max_lds)
+            # hash_ok of this very batch, from the host plan's own seed search (equal to the restatement's: hash_cases.py)
+            ok, _ = _native.debug_plan_seeds(ix, *Q, run.cut)
+            assert ok == H.seeds(Q[0], Q[1], case.dim, case.cw, case.value_type, "SGPU_NO_HASH" in env)[0], (what, ok)
+            facts = dict(SC.plan_facts(case, ix, run, Q), n_cu=n_cu, max_lds=max_lds, hash_ok=ok)
             h = _native.debug_launch_config(heap_factor=run.hf, **facts)
-            # proof of variant: the hook names what the run is there for, and the launch took that workgroup and that much LDS
+            # proof of variant: the hook names what the run is there for, the lane reports that variant and the launch took
+            # that workgroup and that much LDS
             assert (h["block"], h["coop"], h["streamed"]) == (block, 2 if run.coop else 0, 0 if run.coop else 1), (what, h)
             assert stats.block == h["block"] and stats.n_queries == nq, (what, stats.block, stats.n_queries)
+            v = _native.debug_lane_variant(ix)
+            assert v == {k_: h[k_] for k_ in ("lookup", "streamed", "coop", "counted")}, (what, v, h)
             if "SGPU_FORCE_HASH" in run.env:
-                # (taken only if every query has a collision-free seed, which no entry point reports: either answer's bytes)
-                hs = _native.debug_launch_config(heap_factor=run.hf, **dict(facts, hash_ok=1))
-                assert hs["lookup"] == run.expect["lookup"] and stats.lds_bytes in (hs["lds_bytes"], h["lds_bytes"]), (what, hs, stats.lds_bytes)
-            else:
-                for k_, v_ in run.expect.items():
-                    assert h[k_] == v_, (what, k_, h[k_], v_)
-                assert stats.lds_bytes == h["lds_bytes"], (what, stats.lds_bytes, h["lds_bytes"])
+                assert ok == 1, what                   # (every query of these batches has a seed: stage01_cases._check_lookup)
+            for k_, v_ in run.expect.items():
+                assert h[k_] == v_, (what, k_, h[k_], v_)
+            assert stats.lds_bytes == h["lds_bytes"], (what, stats.lds_bytes, h["lds_bytes"])
             if run.cycle and not run.coop:
                 assert stats.grid < nq and np.gcd(stats.grid, len(run.queries)) == 1, (what, stats.grid)   # every workgroup goes on
             _assert_rows(rows, (ws, wi, wn), pick, what)
