@@ -517,6 +517,74 @@ sgpu_status sgpu_facet_counts_host(const sgpu_index* idx, uint32_t slot, const s
                                    uint32_t num_threads, uint32_t* out_values, uint64_t* out_counts, uint32_t* out_n,
                                    uint64_t* out_distinct, uint64_t* out_docs);
 
+/* ---- column aggregations: statistics, histograms, sorted top-k ----------------
+ * Three summaries of the column `slot` (any type) over the documents of `filter` (NULL: all documents), each as a
+ * device call and a host twin that needs no upload, scans the host column with num_threads threads (0 = all) and
+ * DEFINES the result; the device call returns the same bits. Every comparison is made on one unsigned key per type
+ * (U32: the value; I32: the sign bit flipped; F32: the IEEE order of the numbers with -0.0 equal to +0.0), so the two
+ * cannot disagree on one. A stored F32 NaN is not a value: it is counted apart and never ordered. Like the columns,
+ * the results are NOT part of the index file. The device calls run on the column calls' stream under its mutex, read
+ * the column as it is once they hold the mutex, and upload the filter's host words for the call (n_docs / 8 bytes).
+ *
+ * sgpu_column_stats[_host]: docs = |filter| (n_docs for NULL); valid = docs minus the NaNs of an F32 column; min_bits /
+ * max_bits = the smallest / largest value as a bit pattern of the column's type (an f32 zero is reported as +0.0
+ * whichever sign was stored; both 0 where valid == 0); sum_int = U32: the exact sum, I32: the exact i64 sum as two's
+ * complement, F32: 0; sum = U32 / I32: sum_int converted once; F32: the binary64 sum in this canonical order. The
+ * contribution of document d is x[d] = (double)v[d] where d is in the filter and v[d] is not NaN, +0.0 otherwise.
+ *   1. documents are taken in tiles of 16384 consecutive ids;
+ *   2. in tile t, 256 lane sums c[j], j = 0..255, start at +0.0 and add x[t * 16384 + r * 256 + j] for r = 0..63
+ *      ascending (ids at or past n_docs contribute +0.0);
+ *   3. c[j] += c[j + h] for j < h, with h = 128, 64, ..., 1; c[0] is the tile's sum;
+ *   4. the tile sums are added in ascending tile order, starting at +0.0.
+ * Binary64 adds, never contracted or reordered. A NaN result (both infinities among the values) is written as
+ * 0x7ff8000000000000.
+ * Checks, in this order: (1) NULL idx or out, slot >= SGPU_MAX_COLUMNS or empty: SGPU_EINVAL; (2) a filter of another
+ * index: SGPU_EINVAL; (3, device call only) index not uploaded or replica out of range: SGPU_EDEVICE; device memory:
+ * SGPU_ENOMEM, and the index stays usable.
+ *
+ * sgpu_column_histogram[_host]: `edges` holds n_edges bit patterns of the column's type whose values ascend strictly
+ * (n_edges - 1 buckets, at most 4096). numpy.histogram's reading: bucket b counts the documents with
+ * edges[b] <= v < edges[b + 1], and the last bucket also takes v == edges[n_edges - 1]. *out_below counts
+ * v < edges[0], *out_above v > edges[n_edges - 1], *out_nan the NaNs of an F32 column, *out_docs the documents looked
+ * at: sum(out_counts) + below + above + nan == docs always. out_counts has room for n_edges - 1 entries.
+ * Checks, in this order: (1) NULL idx, edges or output, slot >= SGPU_MAX_COLUMNS or empty: SGPU_EINVAL; (2) n_edges
+ * outside 2..4097: SGPU_ELIMIT; (3) an edge that is NaN (F32) or not above the edge before it in the type's order (the
+ * pair -0.0, +0.0 is equal): SGPU_EINVAL, the message names the first offending edge; (4) a filter of another index:
+ * SGPU_EINVAL; (5, device call only) as above.
+ *
+ * sgpu_column_top[_host]: the filter's documents ordered by the column. Rows are the first min(t, valid) documents by
+ * (value ascending for order == 0, descending for order == 1; document id ascending among equal values - -0.0 and
+ * +0.0 are equal). NaN documents never appear. out_doc_ids (native document ids, as sgpu_filter_create takes them)
+ * and out_value_bits (the stored bit patterns) have room for t entries; rows past *out_n are written as zero.
+ * *out_valid and *out_docs are those of the stats.
+ * Checks, in this order: (1) NULL idx or a NULL output, t outside 1..1024, order outside 0..1, slot >=
+ * SGPU_MAX_COLUMNS or empty: SGPU_EINVAL; (2) a filter of another index: SGPU_EINVAL; (3, device call only) as above. */
+struct sgpu_column_stats { /* (a tag only: the call of the same name stands beside it) */
+  uint64_t docs;
+  uint64_t valid;
+  uint32_t min_bits;
+  uint32_t max_bits;
+  uint64_t sum_int;
+  double sum;
+};
+sgpu_status sgpu_column_stats(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter,
+                              struct sgpu_column_stats* out);
+sgpu_status sgpu_column_stats_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t num_threads,
+                                   struct sgpu_column_stats* out);
+sgpu_status sgpu_column_histogram(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter,
+                                  const uint32_t* edges, uint32_t n_edges, uint64_t* out_counts, uint64_t* out_below,
+                                  uint64_t* out_above, uint64_t* out_nan, uint64_t* out_docs);
+sgpu_status sgpu_column_histogram_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter,
+                                       const uint32_t* edges, uint32_t n_edges, uint32_t num_threads,
+                                       uint64_t* out_counts, uint64_t* out_below, uint64_t* out_above, uint64_t* out_nan,
+                                       uint64_t* out_docs);
+sgpu_status sgpu_column_top(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter, uint32_t t,
+                            uint32_t order, uint32_t* out_doc_ids, uint32_t* out_value_bits, uint32_t* out_n,
+                            uint64_t* out_valid, uint64_t* out_docs);
+sgpu_status sgpu_column_top_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t t,
+                                 uint32_t order, uint32_t num_threads, uint32_t* out_doc_ids, uint32_t* out_value_bits,
+                                 uint32_t* out_n, uint64_t* out_valid, uint64_t* out_docs);
+
 /* ---- scores of caller-given documents ----------------------------------------
  * "What does THIS document score for THIS query?": reranking the candidates of another retriever, fusing candidate
  * lists, explaining a hit, re-checking a stored result. The reference has no by-id entry point; its nearest item is

@@ -116,6 +116,13 @@ sgpu_status sgpu_debug_term_filter_stats(sgpu_index* idx, uint32_t replica, doub
 sgpu_status sgpu_debug_column_stats(sgpu_index* idx, uint32_t replica, double* out8);
 /* out2 = {count kernel ms, select kernel ms} of the last sgpu_facet_counts call on `replica`: the two parts of out8[1] above */
 sgpu_status sgpu_debug_facet_kernel_ms(sgpu_index* idx, uint32_t replica, double* out2);
+/* the column aggregations of `replica`: out10 = {kernel ms of the last sgpu_column_stats call, of the last
+ * sgpu_column_histogram call, of the last sgpu_column_top call (all its kernels; HIP events), the grid of the stats
+ * kernel (one workgroup per tile), of the histogram kernel, of the top call's select and emit kernels, the documents of a
+ * tile of the canonical sum (a constant: 16384), the select passes the last top call ran (0 where the filter holds at most
+ * t documents, else 4), the documents per workgroup of the last histogram call and of the last top call}.
+ * SGPU_EINVAL before the replica's first column call */
+sgpu_status sgpu_debug_column_agg_stats(sgpu_index* idx, uint32_t replica, double* out10);
 /* the posting arrays a search on `replica` walks, read back from the device: the replica's own (filter == NULL) or those of
  * the filter's view there, which is obtained as a search obtains it - built on first use or after a new upload or graph,
  * under the filter's mutex; no second build path. sizes5 = {block starts (n_blocks + 1), postings, kNN ids (0: no graph),

@@ -103,6 +103,17 @@ class ColumnClause(C.Structure):
     ]
 
 
+class ColumnStats(C.Structure):   # struct sgpu_column_stats
+    _fields_ = [
+        ("docs", C.c_uint64),
+        ("valid", C.c_uint64),
+        ("min_bits", C.c_uint32),
+        ("max_bits", C.c_uint32),
+        ("sum_int", C.c_uint64),
+        ("sum", C.c_double),
+    ]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_float),

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from ._abi import (ABI_VERSION, BuildConfig, IndexDesc, LaunchStats, SearchParams, SynthSpec,
+from ._abi import (ABI_VERSION, BuildConfig, ColumnStats, IndexDesc, LaunchStats, SearchParams, SynthSpec,
                    SGPU_COL_F32, SGPU_COL_I32, SGPU_COL_U32, SGPU_OK)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -84,6 +84,14 @@ def lib():
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.sgpu_facet_counts_host.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        u64p = C.POINTER(C.c_uint64)
+        L.sgpu_column_stats.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(ColumnStats)]
+        L.sgpu_column_stats_host.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(ColumnStats)]
+        L.sgpu_column_histogram.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, u64p, u64p, u64p, u64p]
+        L.sgpu_column_histogram_host.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p]
+        L.sgpu_column_top.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(C.c_uint32), u64p, u64p]
+        L.sgpu_column_top_host.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(C.c_uint32), u64p,
+                                           u64p]
         L.sgpu_filter_get_bits.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.sgpu_filter_count.argtypes = [vp]
         L.sgpu_filter_count.restype = C.c_uint64
@@ -408,6 +416,61 @@ class NativeIndex:
         if vals[n.value:t].any() or cnts[n.value:t].any():
             raise RuntimeError("facet rows past out_n are not zero")
         return vals[:n.value], cnts[:n.value], int(distinct.value), int(docs.value)
+
+    # ---- column aggregations: statistics, histograms, sorted top-k ----
+    def column_stats(self, slot, filter=None, replica=0, host=False, num_threads=0):
+        """sgpu_column_stats[_host] over the filter's documents (None: all) -> dict(docs, valid, min_bits, max_bits, sum_int,
+        sum, sum_bits): the struct's fields as Python ints, `sum` as a float and `sum_bits` its binary64 pattern."""
+        out = ColumnStats()
+        fh = None if filter is None else _filter_handle(filter)
+        if host:
+            check(lib().sgpu_column_stats_host(self.h, int(slot), fh, int(num_threads), C.byref(out)))
+        else:
+            check(lib().sgpu_column_stats(self.h, int(replica), int(slot), fh, C.byref(out)))
+        return dict(docs=int(out.docs), valid=int(out.valid), min_bits=int(out.min_bits), max_bits=int(out.max_bits),
+                    sum_int=int(out.sum_int), sum=float(out.sum), sum_bits=int(np.array([out.sum], np.float64).view(np.uint64)[0]))
+
+    def column_histogram(self, slot, edges_bits, filter=None, replica=0, host=False, num_threads=0):
+        """sgpu_column_histogram[_host]: `edges_bits` are the edges' u32 bit patterns in the column's type, strictly
+        ascending in its order. Returns (counts u64 [n_edges - 1], below, above, nan, docs)."""
+        e = np.ascontiguousarray(edges_bits, np.uint32).ravel()
+        counts = np.zeros(max(len(e) - 1, 1), np.uint64)
+        below, above, nan, docs = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        fh = None if filter is None else _filter_handle(filter)
+        outs = (_p(counts), C.byref(below), C.byref(above), C.byref(nan), C.byref(docs))
+        if host:
+            check(lib().sgpu_column_histogram_host(self.h, int(slot), fh, _p(e), len(e), int(num_threads), *outs))
+        else:
+            check(lib().sgpu_column_histogram(self.h, int(replica), int(slot), fh, _p(e), len(e), *outs))
+        return counts[:len(e) - 1], int(below.value), int(above.value), int(nan.value), int(docs.value)
+
+    def column_top(self, slot, t=10, order=0, filter=None, replica=0, host=False, num_threads=0):
+        """sgpu_column_top[_host]: the first min(t, valid) documents of the filter (None: all) by (value ascending for order
+        0, descending for 1; id ascending). Returns (doc_ids u32 [n], value_bits u32 [n], valid, docs)."""
+        t, order = int(t), int(order)
+        if not 0 <= t <= 0xffffffff or not 0 <= order <= 0xffffffff:
+            raise ValueError("t = %r / order = %r out of range" % (t, order))
+        ids, vals = np.zeros(max(t, 1), np.uint32), np.zeros(max(t, 1), np.uint32)
+        n, valid, docs = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        fh = None if filter is None else _filter_handle(filter)
+        outs = (_p(ids), _p(vals), C.byref(n), C.byref(valid), C.byref(docs))
+        if host:
+            check(lib().sgpu_column_top_host(self.h, int(slot), fh, t, order, int(num_threads), *outs))
+        else:
+            check(lib().sgpu_column_top(self.h, int(replica), int(slot), fh, t, order, *outs))
+        if ids[n.value:t].any() or vals[n.value:t].any():
+            raise RuntimeError("top rows past out_n are not zero")
+        return ids[:n.value], vals[:n.value], int(valid.value), int(docs.value)
+
+    def debug_column_agg_stats(self, replica=0):
+        """sgpu_debug_column_agg_stats (test hook): what the last column aggregations on `replica` measured."""
+        out = np.zeros(10, np.float64)
+        fn = lib().sgpu_debug_column_agg_stats
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        check(fn(self.h, int(replica), _p(out)))
+        return dict(stats_ms=float(out[0]), hist_ms=float(out[1]), top_ms=float(out[2]), stats_grid=int(out[3]), hist_grid=int(out[4]),
+                    top_grid=int(out[5]), agg_tile=int(out[6]), top_passes=int(out[7]), hist_docs_per_wg=int(out[8]),
+                    top_docs_per_wg=int(out[9]))
 
     def debug_column_stats(self, replica=0):
         """sgpu_debug_column_stats (test hook): what the last column calls on `replica` measured."""

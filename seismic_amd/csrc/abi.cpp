@@ -518,6 +518,32 @@ sgpu_status sgpu_facet_counts_host(const sgpu_index* idx, uint32_t slot, const s
                                    uint64_t* out_docs) {
   return facet_counts_host(idx, slot, filter, t, num_threads, out_values, out_counts, out_n, out_distinct, out_docs);
 }
+sgpu_status sgpu_column_stats(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter, struct sgpu_column_stats* out) {
+  return column_stats_device(idx, replica, slot, filter, out);
+}
+sgpu_status sgpu_column_stats_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t num_threads,
+                                   struct sgpu_column_stats* out) {
+  return column_stats_host(idx, slot, filter, num_threads, out);
+}
+sgpu_status sgpu_column_histogram(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter, const uint32_t* edges,
+                                  uint32_t n_edges, uint64_t* out_counts, uint64_t* out_below, uint64_t* out_above, uint64_t* out_nan,
+                                  uint64_t* out_docs) {
+  return column_histogram_device(idx, replica, slot, filter, edges, n_edges, out_counts, out_below, out_above, out_nan, out_docs);
+}
+sgpu_status sgpu_column_histogram_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, const uint32_t* edges,
+                                       uint32_t n_edges, uint32_t num_threads, uint64_t* out_counts, uint64_t* out_below,
+                                       uint64_t* out_above, uint64_t* out_nan, uint64_t* out_docs) {
+  return column_histogram_host(idx, slot, filter, edges, n_edges, num_threads, out_counts, out_below, out_above, out_nan, out_docs);
+}
+sgpu_status sgpu_column_top(sgpu_index* idx, uint32_t replica, uint32_t slot, const sgpu_filter* filter, uint32_t t, uint32_t order,
+                            uint32_t* out_doc_ids, uint32_t* out_value_bits, uint32_t* out_n, uint64_t* out_valid, uint64_t* out_docs) {
+  return column_top_device(idx, replica, slot, filter, t, order, out_doc_ids, out_value_bits, out_n, out_valid, out_docs);
+}
+sgpu_status sgpu_column_top_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t t, uint32_t order,
+                                 uint32_t num_threads, uint32_t* out_doc_ids, uint32_t* out_value_bits, uint32_t* out_n,
+                                 uint64_t* out_valid, uint64_t* out_docs) {
+  return column_top_host(idx, slot, filter, t, order, num_threads, out_doc_ids, out_value_bits, out_n, out_valid, out_docs);
+}
 sgpu_status sgpu_filter_get_bits(const sgpu_filter* filter, uint32_t* out_words, uint64_t cap_words, uint64_t* n_words) {
   return filter_get_bits(filter, out_words, cap_words, n_words);
 }

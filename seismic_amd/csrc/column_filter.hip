@@ -118,7 +118,9 @@ void column_state_free(ColumnState* s) {
   if (s->device >= 0) (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (DeviceBuffer& c : s->col) c.release();
-  for (DeviceBuffer* b : {&s->f_clauses, &s->f_keys, &s->f_within, &s->f_bits, &s->f_count, &s->c_bits, &s->c_table, &s->c_rows}) b->release();
+  for (DeviceBuffer* b : {&s->f_clauses, &s->f_keys, &s->f_within, &s->f_bits, &s->f_count, &s->c_bits, &s->c_table, &s->c_rows,
+                          &s->a_bits, &s->a_parts, &s->a_edges, &s->a_table, &s->t_state, &s->t_hist, &s->t_waves, &s->t_comps, &s->t_rows})
+    b->release();
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   if (s->ev2) (void)hipEventDestroy(s->ev2);

@@ -1,7 +1,8 @@
 // column_host.cpp — document columns on the host: sgpu_index_set_column / get_column, the argument checks of the column
-// filter and of the facet counts, the plan both twins evaluate (bounds and IN values as keys, columns.hpp) and the two host
-// twins. The host twins define the words and the rows; the device calls (column_filter.hip, facet_counts.hip) return the
-// same.
+// filter, of the facet counts and of the aggregations, the plan both filter twins evaluate (bounds and IN values as keys,
+// columns.hpp) and the host twins: filter, facet counts, stats, histogram, top. The host twins define the words, the
+// rows and the bits; the device calls (column_filter.hip, facet_counts.hip, column_aggregate.hip, column_top.hip) return
+// the same.
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -242,6 +243,230 @@ sgpu_status facet_counts_host(const sgpu_index* idx, uint32_t slot, const sgpu_f
     }
     *out_n = n;
     *out_distinct = keys.size();
+    *out_docs = filter ? filter_count(filter) : n_docs;
+    return SGPU_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+// ---- the aggregations: sgpu_column_stats / _histogram / _top ------------------------------------------------------------
+namespace {
+
+// (the part of check 1 the three calls share: the slot; `call` names the call in the message)
+sgpu_status agg_check_slot(const sgpu_index* idx, uint32_t slot, const char* call) {
+  if (slot >= SGPU_MAX_COLUMNS) return fail(SGPU_EINVAL, "%s: slot %u >= SGPU_MAX_COLUMNS = %u", call, slot, (uint32_t)SGPU_MAX_COLUMNS);
+  if (idx->columns[slot].generation == 0) return fail(SGPU_EINVAL, "%s: slot %u holds no column", call, slot);
+  return SGPU_OK;
+}
+
+inline bool filter_bit(const uint32_t* fbits, uint64_t d) { return !fbits || ((fbits[d >> 5] >> (d & 31u)) & 1u); }
+
+}  // namespace
+
+sgpu_status stats_check_args(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, const struct sgpu_column_stats* out) {
+  if (!idx || !out) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status st = agg_check_slot(idx, slot, "column stats");
+  if (st != SGPU_OK) return st;
+  return foreign_filter(idx, filter);
+}
+
+sgpu_status histogram_check_args(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, const uint32_t* edges, uint32_t n_edges,
+                                 const uint64_t* out_counts, const uint64_t* out_below, const uint64_t* out_above, const uint64_t* out_nan,
+                                 const uint64_t* out_docs) {
+  if (!idx || !edges || !out_counts || !out_below || !out_above || !out_nan || !out_docs) return fail(SGPU_EINVAL, "null argument");
+  const sgpu_status st = agg_check_slot(idx, slot, "column histogram");
+  if (st != SGPU_OK) return st;
+  if (n_edges < 2 || n_edges > kAggMaxBuckets + 1)
+    return fail(SGPU_ELIMIT, "column histogram: n_edges = %u is outside 2..%u", n_edges, kAggMaxBuckets + 1);
+  const uint32_t type = idx->columns[slot].type;
+  for (uint32_t i = 0; i < n_edges; ++i) {
+    if (column_not_a_value(type, edges[i])) return fail(SGPU_EINVAL, "column histogram: edge %u is NaN", i);
+    if (i && column_key(type, edges[i]) <= column_key(type, edges[i - 1]))
+      return fail(SGPU_EINVAL, "column histogram: edge %u is not above edge %u in the column's order", i, i - 1);
+  }
+  return foreign_filter(idx, filter);
+}
+
+sgpu_status top_check_args(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t t, uint32_t order,
+                           const uint32_t* out_doc_ids, const uint32_t* out_value_bits, const uint32_t* out_n, const uint64_t* out_valid,
+                           const uint64_t* out_docs) {
+  if (!idx || !out_doc_ids || !out_value_bits || !out_n || !out_valid || !out_docs) return fail(SGPU_EINVAL, "null argument");
+  if (t == 0 || t > kTopMaxT) return fail(SGPU_EINVAL, "column top: t = %u is outside 1..%u", t, kTopMaxT);
+  if (order > 1) return fail(SGPU_EINVAL, "column top: order = %u is neither 0 (ascending) nor 1 (descending)", order);
+  const sgpu_status st = agg_check_slot(idx, slot, "column top");
+  if (st != SGPU_OK) return st;
+  return foreign_filter(idx, filter);
+}
+
+void stats_combine(uint32_t type, const AggPartial* parts, uint64_t n_tiles, uint64_t docs, struct sgpu_column_stats* out) {
+  double sum = 0.0;
+  uint64_t sum_int = 0, valid = 0;
+  uint32_t min_key = 0xffffffffu, max_key = 0u;
+  for (uint64_t t = 0; t < n_tiles; ++t) {   // (ascending tile order: step 4 of the canonical sum)
+    sum += parts[t].sum;
+    sum_int += parts[t].sum_int;
+    valid += parts[t].valid;
+    if (parts[t].valid) {
+      min_key = std::min(min_key, parts[t].min_key);
+      max_key = std::max(max_key, parts[t].max_key);
+    }
+  }
+  if (type == SGPU_COL_U32) sum = (double)sum_int;
+  else if (type == SGPU_COL_I32) sum = (double)(int64_t)sum_int;
+  else sum_int = 0;
+  if (sum != sum) {
+    const uint64_t quiet = 0x7ff8000000000000ull;
+    std::memcpy(&sum, &quiet, 8);
+  }
+  out->docs = docs;
+  out->valid = valid;
+  out->min_bits = valid ? column_key_bits(type, min_key) : 0u;
+  out->max_bits = valid ? column_key_bits(type, max_key) : 0u;
+  out->sum_int = sum_int;
+  out->sum = sum;
+}
+
+sgpu_status column_stats_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t num_threads,
+                              struct sgpu_column_stats* out) {
+  const sgpu_status cst = stats_check_args(idx, slot, filter, out);
+  if (cst != SGPU_OK) return cst;
+  const HostColumn& col = idx->columns[slot];
+  const uint64_t n_docs = idx->host.n_docs, n_tiles = (n_docs + kAggTile - 1) / kAggTile;
+  const uint32_t* fbits = filter ? filter_host_bits(filter) : nullptr;
+  const uint32_t* v = col.values.data();
+  const uint32_t type = col.type;
+  const int nt = num_threads ? (int)num_threads : default_host_threads(omp_get_max_threads());
+  try {
+    std::vector<AggPartial> parts((size_t)n_tiles);
+#pragma omp parallel for num_threads(nt) schedule(static)
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+      double c[kAggLanes];
+      for (uint32_t j = 0; j < kAggLanes; ++j) c[j] = 0.0;
+      AggPartial p{0.0, 0, 0xffffffffu, 0u, 0u, 0u};
+      const uint64_t d0 = t * kAggTile;
+      for (uint32_t r = 0; r < kAggTile / kAggLanes; ++r)
+        for (uint32_t j = 0; j < kAggLanes; ++j) {
+          const uint64_t d = d0 + (uint64_t)r * kAggLanes + j;
+          if (d >= n_docs || !filter_bit(fbits, d) || column_not_a_value(type, v[d])) continue;
+          const uint32_t key = column_key(type, v[d]);
+          p.min_key = std::min(p.min_key, key);
+          p.max_key = std::max(p.max_key, key);
+          ++p.valid;
+          if (type == SGPU_COL_F32) {
+            float f;
+            std::memcpy(&f, &v[d], 4);
+            c[j] += (double)f;
+          } else {
+            p.sum_int += type == SGPU_COL_I32 ? (uint64_t)(int64_t)(int32_t)v[d] : (uint64_t)v[d];
+          }
+        }
+      for (uint32_t h = kAggLanes / 2; h >= 1; h >>= 1)
+        for (uint32_t j = 0; j < h; ++j) c[j] += c[j + h];
+      p.sum = c[0];
+      parts[(size_t)t] = p;
+    }
+    stats_combine(type, parts.data(), n_tiles, filter ? filter_count(filter) : n_docs, out);
+    return SGPU_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+sgpu_status column_histogram_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, const uint32_t* edges, uint32_t n_edges,
+                                  uint32_t num_threads, uint64_t* out_counts, uint64_t* out_below, uint64_t* out_above, uint64_t* out_nan,
+                                  uint64_t* out_docs) {
+  const sgpu_status cst = histogram_check_args(idx, slot, filter, edges, n_edges, out_counts, out_below, out_above, out_nan, out_docs);
+  if (cst != SGPU_OK) return cst;
+  const HostColumn& col = idx->columns[slot];
+  const uint64_t n_docs = idx->host.n_docs, n_tiles = (n_docs + kAggTile - 1) / kAggTile;
+  const uint32_t* fbits = filter ? filter_host_bits(filter) : nullptr;
+  const uint32_t* v = col.values.data();
+  const uint32_t type = col.type, nb = n_edges - 1, bins = nb + 3;   // bins nb, nb + 1, nb + 2: below, above, NaN
+  const int nt = num_threads ? (int)num_threads : default_host_threads(omp_get_max_threads());
+  try {
+    std::vector<uint32_t> ek(n_edges);
+    for (uint32_t i = 0; i < n_edges; ++i) ek[i] = column_key(type, edges[i]);
+    std::vector<uint64_t> locals((size_t)nt * bins, 0ull);   // (allocated here: nothing throws inside the team)
+#pragma omp parallel num_threads(nt)
+    {
+      uint64_t* mine = locals.data() + (size_t)omp_get_thread_num() * bins;
+#pragma omp for schedule(static)
+      for (uint64_t t = 0; t < n_tiles; ++t) {
+        const uint64_t d1 = std::min<uint64_t>((t + 1) * kAggTile, n_docs);
+        for (uint64_t d = t * kAggTile; d < d1; ++d) {
+          if (!filter_bit(fbits, d)) continue;
+          uint32_t b;
+          if (column_not_a_value(type, v[d])) {
+            b = nb + 2;
+          } else {
+            const uint32_t key = column_key(type, v[d]);
+            if (key < ek[0]) b = nb;
+            else if (key > ek[nb]) b = nb + 1;
+            else b = std::min<uint32_t>((uint32_t)(std::upper_bound(ek.begin(), ek.end(), key) - ek.begin()) - 1u, nb - 1u);
+          }
+          ++mine[b];
+        }
+      }
+    }
+    std::vector<uint64_t> total(bins, 0ull);
+    for (int x = 0; x < nt; ++x)
+      for (uint32_t b = 0; b < bins; ++b) total[b] += locals[(size_t)x * bins + b];
+    for (uint32_t b = 0; b < nb; ++b) out_counts[b] = total[b];
+    *out_below = total[nb];
+    *out_above = total[nb + 1];
+    *out_nan = total[nb + 2];
+    *out_docs = filter ? filter_count(filter) : n_docs;
+    return SGPU_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(SGPU_ENOMEM, "out of host memory");
+  }
+}
+
+sgpu_status column_top_host(const sgpu_index* idx, uint32_t slot, const sgpu_filter* filter, uint32_t t, uint32_t order, uint32_t num_threads,
+                            uint32_t* out_doc_ids, uint32_t* out_value_bits, uint32_t* out_n, uint64_t* out_valid, uint64_t* out_docs) {
+  const sgpu_status cst = top_check_args(idx, slot, filter, t, order, out_doc_ids, out_value_bits, out_n, out_valid, out_docs);
+  if (cst != SGPU_OK) return cst;
+  const HostColumn& col = idx->columns[slot];
+  const uint64_t n_docs = idx->host.n_docs, n_tiles = (n_docs + kAggTile - 1) / kAggTile;
+  const uint32_t* fbits = filter ? filter_host_bits(filter) : nullptr;
+  const uint32_t* v = col.values.data();
+  const uint32_t type = col.type;
+  const int nt = num_threads ? (int)num_threads : default_host_threads(omp_get_max_threads());
+  try {
+    // the rows are the t smallest composites (key, or ~key for descending) << 32 | id: distinct, so fully determined.
+    // A thread keeps the t smallest of its tiles (cut back whenever 4 t have gathered); the threads' lists are merged.
+    std::vector<std::vector<uint64_t>> lists((size_t)nt);
+    for (std::vector<uint64_t>& l : lists) l.reserve(4 * (size_t)t + kAggTile);   // (allocated here: nothing throws inside the team)
+    uint64_t valid = 0;
+#pragma omp parallel num_threads(nt) reduction(+ : valid)
+    {
+      std::vector<uint64_t>& mine = lists[(size_t)omp_get_thread_num()];
+#pragma omp for schedule(static)
+      for (uint64_t tl = 0; tl < n_tiles; ++tl) {
+        const uint64_t d1 = std::min<uint64_t>((tl + 1) * kAggTile, n_docs);
+        for (uint64_t d = tl * kAggTile; d < d1; ++d) {
+          if (!filter_bit(fbits, d) || column_not_a_value(type, v[d])) continue;
+          ++valid;
+          const uint32_t key = column_key(type, v[d]);
+          mine.push_back((uint64_t)(order ? ~key : key) << 32 | (uint32_t)d);
+        }
+        if (mine.size() > 4 * (size_t)t) {
+          std::nth_element(mine.begin(), mine.begin() + t, mine.end());
+          mine.resize(t);
+        }
+      }
+    }
+    std::vector<uint64_t> all;
+    for (const std::vector<uint64_t>& l : lists) all.insert(all.end(), l.begin(), l.end());
+    const uint32_t n = (uint32_t)std::min<uint64_t>(t, all.size());
+    std::partial_sort(all.begin(), all.begin() + n, all.end());
+    for (uint32_t i = 0; i < t; ++i) {
+      out_doc_ids[i] = i < n ? (uint32_t)all[i] : 0u;
+      out_value_bits[i] = i < n ? v[(uint32_t)all[i]] : 0u;
+    }
+    *out_n = n;
+    *out_valid = valid;
     *out_docs = filter ? filter_count(filter) : n_docs;
     return SGPU_OK;
   } catch (const std::bad_alloc&) {

@@ -250,6 +250,15 @@ sgpu_status sgpu_debug_facet_kernel_ms(sgpu_index* idx, uint32_t replica, double
   return last_call(facet_debug_kernel_ms, idx, replica, out2, "column");
 }
 
+// (not part of the boundary: the column aggregations of `replica` - out10 = {kernel ms of the last sgpu_column_stats /
+// _histogram / _top call, the grid of each (top: of its select and emit kernels), kAggTile, the select passes the last top
+// call ran, the documents per workgroup of the last histogram and top call}; SGPU_EINVAL before the replica's first column
+// call. tools/column_agg_probe.py)
+sgpu_status sgpu_debug_column_agg_stats(sgpu_index* idx, uint32_t replica, double* out10) {
+  SGPU_HOOK_OR(SGPU_EINVAL);
+  return last_call(column_agg_debug_stats, idx, replica, out10, "column");
+}
+
 // (not part of the boundary: device and wall milliseconds of the build of the filter's view on `replica`; SGPU_EINVAL
 // before it is built. tools/filter_probe.py)
 sgpu_status sgpu_debug_filter_build_times(const sgpu_filter* filter, uint32_t replica, double* out2) {

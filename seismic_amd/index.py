@@ -635,6 +635,56 @@ class _ScoreMixin:
         vals, cnts, distinct, docs = self._ix.facet_counts(slot, _native_filter(self, filter), top, host=host)
         return list(zip(vals.tolist(), cnts.tolist())), distinct, docs
 
+    # ---- column aggregations (sgpu_column_stats, sgpu_column_histogram, sgpu_column_top) ----
+    def _agg_call(self, name, filter, device):
+        slot, dt = self._column(name)
+        host = device is False or (device is None and not self._uploaded)
+        if not host:
+            self._ensure_device()
+        return slot, dt, _native_filter(self, filter), host
+
+    def stats(self, name, filter=None, device=None):
+        """Summary of column `name` over the filter's documents (None: all) -> dict(docs, valid, min, max, sum, mean):
+        `valid` leaves out the NaNs of an f32 column; min / max in the column's dtype (None where valid == 0; an f32 zero
+        comes back as +0.0); sum an exact Python int for u32 / i32 and the canonical binary64 sum for f32; mean =
+        sum / valid, None where valid == 0 (sgpu_column_stats). device as for make_column_filter."""
+        slot, dt, f, host = self._agg_call(name, filter, device)
+        s = self._ix.column_stats(slot, f, host=host)
+        valid = s["valid"]
+        lo, hi = np.array([s["min_bits"], s["max_bits"]], np.uint32).view(dt).tolist()
+        if dt == np.float32:
+            total = s["sum"]
+        else:
+            total = s["sum_int"] - (1 << 64) if dt == np.int32 and s["sum_int"] >> 63 else s["sum_int"]
+        return dict(docs=s["docs"], valid=valid, min=lo if valid else None, max=hi if valid else None, sum=total,
+                    mean=total / valid if valid else None)
+
+    def histogram(self, name, edges, filter=None, device=None):
+        """Counts of column `name` per range, numpy.histogram's reading -> dict(counts, below, above, nan, docs): `edges`
+        (2 .. 4097 values of the column's dtype, strictly ascending) bound len(edges) - 1 buckets, bucket b holding
+        edges[b] <= v < edges[b + 1] and the last one v == edges[-1] too; below / above count the values outside, nan the
+        NaNs of an f32 column (sgpu_column_histogram). An edge the column's integer type cannot hold raises ValueError.
+        device as for make_column_filter."""
+        slot, dt, f, host = self._agg_call(name, filter, device)
+        bits = []
+        for e in (edges.tolist() if isinstance(edges, np.ndarray) else list(edges)):
+            if e != e:
+                raise ValueError("an edge is NaN")
+            lo, hi = _column_bounds(dt, e, e)      # (an integer type: ceil and floor agree only on a value it holds)
+            if lo != hi:
+                raise ValueError("edge %r is not a value of the column's type %s" % (e, np.dtype(dt).name))
+            bits.append(lo)
+        counts, below, above, nan, docs = self._ix.column_histogram(slot, np.asarray(bits, np.uint32), f, host=host)
+        return dict(counts=counts.astype(np.int64), below=below, above=above, nan=nan, docs=docs)
+
+    def top_by(self, name, k=10, descending=False, filter=None, device=None):
+        """The filter's documents (None: all) ordered by column `name` -> (ids, values): the first k (1 .. 1024) by value
+        ascending (descending=True: descending), equal values by the index's document order; NaN documents never appear.
+        ids as the results name them, values in the column's dtype (sgpu_column_top). device as for make_column_filter."""
+        slot, dt, f, host = self._agg_call(name, filter, device)
+        rows, bits, _, _ = self._ix.column_top(slot, k, 1 if descending else 0, f, host=host)
+        return [self._score_name(r) for r in rows.tolist()], bits.view(dt)
+
     def batch_collapse(self, query_components, query_values, doc_ids_per_query, groups_per_query, k, m=1, device=None, groups=None):
         """Field collapsing -> [[(group, score, best_doc_id, best_score, members)]]: per query the k (1 .. 1024) best
         groups of its candidates (as for batch_score, at most 4096 per query). groups_per_query[q][i] is the u32 group
